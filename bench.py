@@ -7,7 +7,7 @@ ADE/FDE sums) over one batch of synthetic ETH-shaped scenes, inputs resident
 in HBM.  This is "reference mode": the reference's train.py loop has no loss
 or backward (SURVEY.md finding 5).  The build's train mode (the same step +
 loss gradient + one gradient all-reduce + RMSProp) is timed beside it under
-"train_mode", with its own roofline.
+"train_mode", with its own roofline, when ``--full`` is given.
 Workload = BASELINE.json configs[1]: "eth_hotel_synth" (S=256 scenes per
 rank, Nmax=32 peds, H=128, F=20 frames).  Weak scaling: every rank owns its
 own 256 scenes (seeded per rank); reference mode has no data-path collective
@@ -17,6 +17,17 @@ Inputs rotate over K device-resident batches whose total exceeds the 256 MiB
 Infinity Cache (``--rotate``), so the HBM figure is not served on-die.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME]
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(``ms_per_step``: the milliseconds one timed step took).  ``--dump-outputs
+DIR`` then writes what the last timed step computed (pred, h, metrics of its
+batch: the arrays a caller of the step receives) as DIR/<name>.npy; inputs
+are seeded, so two builds can be compared output for output.  ``--full``
+adds everything else the benchmark measures, each in runs of its own: the CPU
+baseline, the one-launch roofline of the reference-mode kernel, and train
+mode with its roofline and collective parts (``cpu_baseline``, ``roofline``
+and ``train_mode`` are null in a plain run's line).
 
 With N > 1 and no WORLD_SIZE in the environment this process launches N
 ranks itself (``python -m torch.distributed.run``, one rank per GPU, RCCL)
@@ -466,6 +477,26 @@ def real_scene_batch(S, H, rank, world):
                       n_frames=h["n_frames"], ped_mask=h["ped_mask"])
 
 
+DUMP_LIMIT = 64 * 2 ** 20       # --dump-outputs: bytes in all
+
+
+def dump_outputs(path, out):
+    """--dump-outputs: the step's outputs (fs.StepOutputs: pred, h, metrics)
+    as <path>/<name>.npy, float32 as computed.  At most DUMP_LIMIT bytes in
+    all: an array over its equal share of that is written as a fixed sample,
+    its flat entries at sorted indices drawn without replacement by
+    numpy.random.default_rng(0) (the same entries in every run)."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: getattr(out, k).detach().float().cpu().numpy() for k in ("pred", "h", "metrics")}
+    share = DUMP_LIMIT // len(arrs)
+    whole = sum(a.nbytes for a in arrs.values()) <= DUMP_LIMIT
+    for k, a in arrs.items():
+        if not whole and a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+
+
 def selftest_worker(args, world, rank):
     """--selftest-launcher (CPU, gloo): the launcher, the process-group check,
     the timing brackets and the metric all-reduce, with a no-op step in place
@@ -496,11 +527,18 @@ def main(argv=None):
     ap.add_argument("--scenes", type=int, default=0, help="override scenes per rank")
     ap.add_argument("--rotate", type=int, default=0,
                     help="input batches to rotate over (0: enough to exceed the 256 MiB MALL)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, in runs of their "
+                         "own: the CPU baseline, the reference-mode kernel's one-launch roofline, "
+                         "train mode (off: those fields of the line are null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs (pred, h, "
+                         "metrics; rank 0's) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-budget", type=float, default=10.0)
     ap.add_argument("--cpu-procs", type=int, default=0,
                     help="processes of the all-core CPU aggregate (0: the CPUs this job may use)")
-    ap.add_argument("--no-train", action="store_true", help="skip the train-mode timing")
+    ap.add_argument("--no-train", action="store_true", help="--full: skip the train-mode timing")
     ap.add_argument("--loss", choices=("l2", "nll"), default="l2",
                     help="train-mode loss: 1/2 squared error or the bivariate-Gaussian NLL")
     ap.add_argument("--pred-layout", choices=("ped", "band"), default="ped",
@@ -534,6 +572,8 @@ def main(argv=None):
                          "collective included, from one HIP graph (the default)")
     ap.add_argument("--selftest-launcher", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args, argv)
@@ -560,7 +600,7 @@ def main(argv=None):
     # CPU baseline first: its worker processes are spawned before this
     # process initialises the GPU
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         procs = args.cpu_procs or job_cpus()
         cpu = cpu_baseline(args.config, b, params_host.numpy(), args.cpu_budget, procs)
 
@@ -618,37 +658,42 @@ def main(argv=None):
     def step(i):
         plans[i % K].run()
 
+    # the last timed step's index (its batch's outputs are what --dump-outputs
+    # writes): the graph's timed steps follow its max(W, 1) warm-up steps
     if args.no_graph:
+        last = args.steps - 1
         elapsed = timed(step, args.steps, args.warmup, dist, torch.cuda.synchronize)
     else:
+        last = max(args.warmup, 1) + args.steps - 1
         # (a process group is up: its watchdog thread queries events while we
         # capture, so the capture is thread-local)
         elapsed, gm = timed_graph(step, args.steps, args.warmup, dist, torch.cuda.synchronize, stream,
                                   side=streams[1:], thread_local=dist is not None)
-    # reference mode: replicas only; the ADE/FDE numerators of the last batch
-    # are summed across ranks once at the end
-    tot = plans[(args.steps - 1) % K].out.metrics.double().sum(dim=0)
+    # reference mode: replicas only; the ADE/FDE numerators of the last timed
+    # step's batch are summed across ranks once at the end
+    tot = plans[last % K].out.metrics.double().sum(dim=0)
     if dist is not None:
         dist.all_reduce(tot)
-    # the roofline's time: ONE launch's duration, launches back to back on
-    # one stream (no overlap; what rocprofv3 reports per dispatch), over the
-    # batches of stream 0
-    R = max(20, min(args.steps, 200))
-    one = [plans[k] for k in range(0, K, len(streams))]
-    if args.no_graph:
-        kern_s = event_time(lambda i: one[i % len(one)].run(), R, stream)
-    else:
-        kern_s = graph_event_time(GraphSteps(lambda i: one[i % len(one)].run(), R, stream,
-                                             thread_local=dist is not None), stream)
-    aflops = algorithmic_flops(b, H)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, plans[last % K].out)
 
-    train = None
-    if not args.no_train:
+    kern_s = train = None
+    if args.full:
+        # the roofline's time: ONE launch's duration, launches back to back on
+        # one stream (no overlap; what rocprofv3 reports per dispatch), over the
+        # batches of stream 0
+        R = max(20, min(args.steps, 200))
+        one = [plans[k] for k in range(0, K, len(streams))]
+        if args.no_graph:
+            kern_s = event_time(lambda i: one[i % len(one)].run(), R, stream)
+        else:
+            kern_s = graph_event_time(GraphSteps(lambda i: one[i % len(one)].run(), R, stream,
+                                                 thread_local=dist is not None), stream)
+    if args.full and not args.no_train:
         train = time_train(args, params, batches, dev, dist, S, F, H, world, b, pbytes, K, layout,
                            stream)
 
     if rank == 0:
-        pmc = load_pmc(args.config)
         m = tot.cpu().numpy()
         line = {
             "metric": METRIC,
@@ -683,18 +728,22 @@ def main(argv=None):
                        "streams": len(streams),
                        "launch": "host launch per step" if args.no_graph else
                                  "HIP graph of the timed steps (one replay)"},
-            # achieved: one launch alone (kern_s); *_per_step: the timed steps'
-            # effective rate (launches overlap on streams / co-resident
-            # workgroups, so it exceeds one launch's rate)
-            "roofline": dict(roofline(abytes, aflops, kern_s, elapsed / args.steps),
-                             traffic=pmc[0], traffic_source=pmc[1],
-                             kernel="g2k_step_fused_f32 (g2k_scene_kernel)",
-                             kernel_us=kern_s * 1e6),
+            "roofline": None,
             "cpu_baseline": cpu,
             "ade_fde_all_ranks": {"ADE": float(m[0] / max(m[1], 1)),
                                   "FDE_frob_per_frame": float(np.sqrt(m[2]) / max(m[5], 1))},
             "train_mode": train,
         }
+        if kern_s is not None:
+            # achieved: one launch alone (kern_s); *_per_step: the timed steps'
+            # effective rate (launches overlap on streams / co-resident
+            # workgroups, so it exceeds one launch's rate)
+            pmc = load_pmc(args.config)
+            line["roofline"] = dict(roofline(abytes, algorithmic_flops(b, H), kern_s,
+                                             elapsed / args.steps),
+                                    traffic=pmc[0], traffic_source=pmc[1],
+                                    kernel="g2k_step_fused_f32 (g2k_scene_kernel)",
+                                    kernel_us=kern_s * 1e6)
         if cpu:
             v = line["value"]
             line["speedup_vs_cpu"] = {"one_thread": v / cpu["value"],

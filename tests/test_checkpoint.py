@@ -3,8 +3,9 @@ SURVEY.md §8(f) row 3, Appendix D).  Pinned byte for byte by the reference's
 own checkpoint save/g2k_mcr_model_val_0.ckpt-0 (copied as data into
 tests/golden/ckpt_val0.*): decoding then re-encoding it reproduces both files
 exactly (table layout, restart points, masked CRC32Cs, key successor, footer).
-When /root/reference is present (build container only) all eight reference
-checkpoints are re-encoded the same way."""
+All eight reference checkpoints, stored byte for byte in
+tests/golden/ckpt_bundle_*.npz (tools/make_fixtures.py), are re-encoded the
+same way."""
 import glob
 import os
 
@@ -39,11 +40,15 @@ def test_reencode_reference_checkpoint_byte_exact(tmp_path):
     _same_bytes(GOLD, out)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/save"), reason="reference checkpoints absent")
 def test_reencode_all_reference_checkpoints(tmp_path):
-    prefixes = sorted(p[:-6] for p in glob.glob("/root/reference/save/*.index"))
-    assert len(prefixes) == 8
-    for i, prefix in enumerate(prefixes):
+    stored = sorted(glob.glob(os.path.join(os.path.dirname(GOLD), "ckpt_bundle_*.npz")))
+    assert len(stored) == 8
+    for i, npz in enumerate(stored):
+        prefix = str(tmp_path / f"ref{i}")
+        with np.load(npz) as z:
+            for key, ext in (("index", ".index"), ("data", ".data-00000-of-00001")):
+                with open(prefix + ext, "wb") as f:
+                    f.write(z[key].tobytes())
         out = str(tmp_path / f"c{i}")
         ck.write_bundle(out, ck.read_bundle(prefix))
         _same_bytes(prefix, out)

@@ -157,11 +157,12 @@ def test_capture_right_after_eager_collectives(gpu):
 
 @pytest.mark.parametrize("capture", [False, True], ids=["host_launches", "captured"])
 def test_bench_collective_structure(gpu, capture):
-    """bench.py --collective on: the train line reports the gradient ->
+    """bench.py --full --collective on: the train line reports the gradient ->
     all-reduce -> update structure and its parts' times; one HIP graph with
     the collective captured by default, host launches with --eager-collective."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--collective", "on", "--steps", "10",
-           "--warmup", "3", "--no-cpu-baseline", "--config", "eth_hotel_synth", "--rotate", "4"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--collective", "on",
+           "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--config", "eth_hotel_synth",
+           "--rotate", "4"]
     if not capture:
         cmd.append("--eager-collective")
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")

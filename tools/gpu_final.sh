@@ -6,5 +6,5 @@ timeout -k 10 700 python -u -m pytest tests -x -q -m gpu --timeout 200 --timeout
 tail -2 $O/pytest.log
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { echo "smoke failed"; cat $O/smoke.log; exit 1; }
 tail -3 $O/smoke.log
-timeout -k 10 400 python bench.py > $O/bench.log 2>&1 || { echo "bench failed"; tail -20 $O/bench.log; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/bench.log 2>&1 || { echo "bench failed"; tail -20 $O/bench.log; exit 1; }
 grep '^{' $O/bench.log | cut -c1-600

@@ -5,9 +5,9 @@ set -o pipefail
 O=gpurun_out/r10a; mkdir -p $O
 timeout -k 10 400 python -u -m pytest tests/test_rccl_gpu.py tests/test_split_gpu.py tests/test_abi.py -x -v --timeout 240 --timeout-method thread > $O/rccl.log 2>&1 || { echo "rccl tests failed"; tail -60 $O/rccl.log; exit 1; }
 grep -E "PASSED|FAILED|passed|failed" $O/rccl.log
-timeout -k 10 300 python bench.py > $O/bench.log 2>&1 || { echo "bench failed"; tail -30 $O/bench.log; exit 1; }
+timeout -k 10 300 python bench.py --full > $O/bench.log 2>&1 || { echo "bench failed"; tail -30 $O/bench.log; exit 1; }
 grep '^{' $O/bench.log > $O/bench.json
-timeout -k 10 300 python bench.py --collective on --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_coll.log 2>&1 || { echo "bench coll failed"; tail -30 $O/bench_coll.log; exit 1; }
+timeout -k 10 300 python bench.py --full --collective on --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_coll.log 2>&1 || { echo "bench coll failed"; tail -30 $O/bench_coll.log; exit 1; }
 grep '^{' $O/bench_coll.log > $O/bench_coll.json
 python - <<'PY'
 import json

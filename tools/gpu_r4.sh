@@ -9,7 +9,7 @@ rc=$?; tail -3 $O/pytest.log; grep FAILED $O/pytest.log
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || { echo "pytest rc $rc"; exit 1; }
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { echo "smoke failed"; cat $O/smoke.log; exit 1; }
 tail -2 $O/smoke.log
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $O/bench.log 2>&1 || { echo "bench failed"; tail -20 $O/bench.log; exit 1; }
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $O/bench.log 2>&1 || { echo "bench failed"; tail -20 $O/bench.log; exit 1; }
 grep '^{' $O/bench.log | cut -c1-400
 for x in "$@"; do
 case $x in

@@ -10,6 +10,6 @@ P2="SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_WAVE_
 i=0
 for P in "$P1" "$P2"; do
   i=$((i+1))
-  timeout -s KILL 150 rocprofv3 --pmc $P --output-format csv -d $O/p$i -o run -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline "$@" > $O/p$i.log 2>&1 || { echo "pass $i failed"; tail -5 $O/p$i.log; exit 1; }
+  timeout -s KILL 150 rocprofv3 --pmc $P --output-format csv -d $O/p$i -o run -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline "$@" > $O/p$i.log 2>&1 || { echo "pass $i failed"; tail -5 $O/p$i.log; exit 1; }
 done
 python tools/pmc_sq.py $O/p1 $O/p2 | tee $O/sq_summary.txt

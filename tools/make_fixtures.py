@@ -359,6 +359,24 @@ def make_gridlstm_fixture():
     return names
 
 
+def make_ckpt_bundle_fixtures():
+    """Every checkpoint of the reference's save/ as stored bytes: one
+    ckpt_bundle_<prefix>.npz per bundle holding its .index and its
+    .data-00000-of-00001 file as uint8 arrays (deflated: the largest data
+    file, 2.6 MB raw, stays under the size limit of a committed file).
+    tests/test_checkpoint.py re-encodes each and compares byte for byte."""
+    import glob
+    made = []
+    for idx in sorted(glob.glob(os.path.join(REF, "save", "*.index"))):
+        prefix = idx[:-len(".index")]
+        parts = {k: np.frombuffer(open(prefix + ext, "rb").read(), np.uint8)
+                 for k, ext in (("index", ".index"), ("data", ".data-00000-of-00001"))}
+        name = f"ckpt_bundle_{os.path.basename(prefix)}.npz"
+        np.savez_compressed(os.path.join(OUT, name), **parts)
+        made.append(name)
+    return made
+
+
 def main():
     if not os.path.isdir(REF):
         print("no /root/reference here: fixtures are committed, nothing to do")
@@ -366,6 +384,9 @@ def main():
     os.makedirs(OUT, exist_ok=True)
     if "--ckpt-only" in sys.argv:
         print("attn in range(ngh): max residual, min cost / attn mismatch:", make_attn_range_fixture())
+        return
+    if "--bundles-only" in sys.argv:
+        print("checkpoint bundles:", make_ckpt_bundle_fixtures())
         return
     for name, rel in DATASETS.items():
         rec = make_data_fixture(name, rel)
@@ -375,6 +396,7 @@ def main():
     print("gridlstm weights:", make_gridlstm_fixture())
     print("mcrAttn model copy:", make_ckpt_scope_fixture())
     print("attn in range(ngh): max residual, min cost / attn mismatch:", make_attn_range_fixture())
+    print("checkpoint bundles:", make_ckpt_bundle_fixtures())
 
 
 if __name__ == "__main__":
