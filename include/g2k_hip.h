@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define G2K_ABI_VERSION 9
+#define G2K_ABI_VERSION 10
 
 enum {
   G2K_OK = 0,
@@ -407,6 +407,32 @@ int g2k_nll_f32(const g2k_dims* d, const float* pred, const float* targets,
                 int64_t workspace_bytes, void* stream);
 int g2k_gauss_sample_f32(const g2k_dims* d, const float* pred, const float* head, uint64_t seed,
                          float* out, void* stream);
+
+/*
+ * Best-of-K sampling evaluation of the head (minADE_K / minFDE_K; ABI 10;
+ * csrc/g2k_bestk.hip), one pass over pred and targets, no draw in memory.
+ * Inputs as the NLL's; targets [S, 1, Nmax, L, 2] with G2K_STEP_TARGETS_SHARED
+ * in d->flags (the only flag read; d->S, F, Nmax the only sizes).  A pair is
+ * (s, f, n) with f < n_frames[s], n < n_active[s], ped_mask[s][n] != 0.
+ *   draw k (k < K) = what the sampler writes for seed (seed + k) mod 2^64
+ *   ADE_k = 1/12 sum_t |draw_k(t) - target(t)|_2, FDE_k = |draw_k(11) - target(11)|_2
+ *   minADE = min_k ADE_k, minFDE = min_k FDE_k, kA / kF the lowest k attaining them
+ *   per_ped [S, F, Nmax, 4] or NULL: {minADE, minFDE, kA, kF}, zeros for
+ *     non-pairs (every element written; 16-byte aligned)
+ *   best [S, F, 2L, Nmax] or NULL: draw kA for pairs, pred elsewhere (every
+ *     element written)
+ *   out [S, 8] = {sum minADE, sum minFDE, pairs, sum ADE(pred), sum FDE(pred),
+ *     K, 0, 0} over the scene's pairs, fixed order (ADE / FDE(pred): the mean
+ *     prediction's, metrics[3] / [4] of the fused step)
+ * K in 1..4096, Nmax in 1..256, workspace >= g2k_best_of_k_workspace_bytes(d)
+ * (else G2K_EINVAL before any launch); S = 0 is a no-op.  Asynchronous, no
+ * allocation, capturable.
+ */
+int64_t g2k_best_of_k_workspace_bytes(const g2k_dims* d);
+int g2k_best_of_k_f32(const g2k_dims* d, const float* pred, const float* targets,
+                      const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                      const float* head, uint64_t seed, int32_t K, float* per_ped, float* best,
+                      float* out, void* workspace, int64_t workspace_bytes, void* stream);
 
 int64_t g2k_context_conv_workspace_bytes(int32_t Hh, int32_t Ww, int32_t D);
 int g2k_context_conv_f32(const float* img, int32_t Hh, int32_t Ww, int32_t C, const float* filt,

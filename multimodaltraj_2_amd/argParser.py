@@ -1,7 +1,8 @@
 """Flags of the reference (argParser.py:3-73), same names and defaults, plus
 the build's own: --data_root (Q8), --device, --mode,
 --world_size, --n_max, --train_batch, --train_scenes, --valid_from_seed,
---log_dir, --save_dir, --seed, --use_grid_lstm."""
+--log_dir, --save_dir, --seed, --use_grid_lstm, --loss, --num_samples,
+--sample_seed, --head_log_sigma."""
 import argparse
 
 
@@ -45,6 +46,15 @@ class ArgsParser:
     parser.add_argument('--loss', choices=('l2', 'nll'), default='l2',
                         help='--mode train: 1/2 squared error of the predictions, or the '
                              'bivariate-Gaussian NLL with a learned per-step head')
+    parser.add_argument('--num_samples', type=int, default=0,
+                        help='best-of-K sampling evaluation on the left-out dataset with K draws '
+                             'of the Gaussian head (minADE_K / minFDE_K; --mode train runs it after '
+                             'the last epoch; 0: off)')
+    parser.add_argument('--sample_seed', type=int, default=0,
+                        help='--num_samples: seed of draw 0 (draw k uses seed + k)')
+    parser.add_argument('--head_log_sigma', type=float, default=0.0,
+                        help="--num_samples: log sigma of the head when the parameters hold none "
+                             "(an L2-trained checkpoint)")
     parser.add_argument('--train_scenes', type=int, default=0,
                         help='--mode train: distinct scenes used (0: all of the fold)')
     parser.add_argument('--valid_from_seed', type=int, default=0,

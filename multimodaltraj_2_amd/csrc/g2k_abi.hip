@@ -490,6 +490,34 @@ int g2k_gauss_sample_f32(const g2k_dims* d, const float* pred, const float* head
   return gauss_sample_launch(d, pred, head, seed, out, (hipStream_t)stream);
 }
 
+int64_t g2k_best_of_k_workspace_bytes(const g2k_dims* d) {
+  if (!d || d->S < 0 || d->F < 0) return -1;
+  return best_of_k_ws_bytes(d);
+}
+
+int g2k_best_of_k_f32(const g2k_dims* d, const float* pred, const float* targets,
+                      const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                      const float* head, uint64_t seed, int32_t K, float* per_ped, float* best,
+                      float* out, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!d) return set_err(G2K_EINVAL, "dims is NULL");
+  if (d->flags & G2K_STEP_PRED_PED_MAJOR)
+    return set_err(G2K_EUNSUPPORTED, "best_of_k reads pred_path_band [S, F, 2L, Nmax]");
+  if (d->S < 0 || d->F < 0 || d->Nmax < 1 || d->Nmax > kMaxN)
+    return set_err(G2K_EINVAL, "S=%d F=%d Nmax=%d", d->S, d->F, d->Nmax);
+  if (K < 1 || K > 4096) return set_err(G2K_EINVAL, "K=%d (1..4096)", K);
+  if (!pred || !targets || !n_active || !head || !out)
+    return set_err(G2K_EINVAL, "a required buffer pointer is NULL");
+  if (((uintptr_t)targets) & 7) return set_err(G2K_EINVAL, "targets must be 8-byte aligned");
+  if (((uintptr_t)per_ped) & 15) return set_err(G2K_EINVAL, "per_ped must be 16-byte aligned");
+  const int64_t need = best_of_k_ws_bytes(d);
+  if (d->S > 0 && (!workspace || workspace_bytes < need))
+    return set_err(G2K_EINVAL, "workspace of %lld bytes needed (got %lld)", (long long)need,
+                   (long long)workspace_bytes);
+  if (d->S == 0) return G2K_OK;
+  return best_of_k_launch(d, pred, targets, n_active, n_frames, ped_mask, head, seed, K, per_ped,
+                          best, out, static_cast<float*>(workspace), (hipStream_t)stream);
+}
+
 int g2k_update_f32(float* params, float* ms, const float* grad, int64_t n_params, float lr,
                    float decay, float grad_clip, void* stream) {
   if (!params || !grad || n_params < 0 || n_params > (1 << 30))

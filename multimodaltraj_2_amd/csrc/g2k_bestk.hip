@@ -1,0 +1,260 @@
+// g2k_bestk.hip — fused best-of-K sampling evaluation (minADE_K / minFDE_K)
+// of the bivariate-Gaussian head (g2k_nll.hip).  The build's: the reference
+// has no probabilistic head, so PARITY UNPINNED; tests/bestk_ref.py restates
+// the definition over oracle/g2k_ref.py gauss_sample.
+//
+// Definition.  Inputs as g2k_nll_f32: pred [S, F, 2L, Nmax] (band layout),
+// targets [S, F, Nmax, L, 2] ([S, 1, Nmax, L, 2] with G2K_STEP_TARGETS_SHARED),
+// n_active [S], n_frames [S] or NULL, ped_mask [S, Nmax] or NULL, head [3, 12],
+// seed (uint64), K in [1, 4096].  A pair is (s, f, n) with f < n_frames[s],
+// n < n_active[s], ped_mask[s][n] != 0 (the pairs of the a9 errors and of both
+// train losses).
+//   draw k (k = 0..K-1) = what g2k_gauss_sample_f32 writes for seed
+//     (seed + k) mod 2^64: element e = ((s F + f) 12 + t) Nmax + n through
+//     gauss_draw (g2k_common.h), the sampler's own code
+//   ADE_k(s,f,n) = 1/12 sum_t ||draw_k(t) - target(t)||_2
+//   FDE_k        = ||draw_k(11) - target(11)||_2
+//   minADE = min_k ADE_k, minFDE = min_k FDE_k (independently); kA / kF the
+//     lowest k attaining each (ties to the lowest index: the result does not
+//     depend on how the draws are shared out over lanes)
+// Outputs: per_ped [S, F, Nmax, 4] = {minADE, minFDE, kA, kF} (zeros for
+// non-pairs, every element written) or NULL; best [S, F, 2L, Nmax] = draw kA
+// for pairs, pred elsewhere (every element written; the draw is regenerated
+// from the counter, never stored along the way) or NULL; out [S, 8] =
+// {sum minADE, sum minFDE, pairs, sum ADE(pred), sum FDE(pred), K, 0, 0} over
+// the scene's pairs (ADE / FDE(pred): the same formulas on the mean, the fused
+// step's metrics[3] / [4]), fixed summation order.
+//
+// Geometry.  One workgroup of 256 threads per (scene, chunk of FC frames).  A
+// work item is (pair, slice): the K draws of a pair are dealt round-robin to
+// KS = 2^j adjacent lanes (k = slice, slice + KS, ...); each lane holds the
+// pair's 12 means and 12 targets in registers, draws in registers and keeps
+// its running minima; the KS lanes' minima are combined by a butterfly on
+// (value, index), lexicographic, so the lowest k wins a tie whatever KS is.
+// KS and FC come from the shapes alone (bestk_geom): KS grows until the launch
+// has ~2 * 256 CUs * 1024 items or K is used up, FC fills the 256 threads —
+// S 256 x F 20 x Nmax 32 runs KS 4, FC 2 (2560 workgroups), real-data
+// evaluation (F 1, n_active down to 2, K 20) runs KS 16 (a pair per quarter
+// wave).  The items of a chunk are its PAIRS' (columns >= n_active and frames
+// >= n_frames never reach the hash); non-pairs only get their zeros / copy.
+// Scene sums: per-workgroup rows [S * C][8] in the caller's workspace, then
+// g2k_bestk_rows_kernel adds a scene's C rows in chunk order (no atomics);
+// C == 1 writes out directly.
+#include "g2k_common.h"
+
+namespace g2k {
+namespace {
+
+constexpr int kBkThreads = 256;
+constexpr int64_t kBkFill = 2 * 256 * 1024;   // items that fill 256 CUs twice over
+constexpr int kBkMaxSlices = 64;              // one wave: the combine is lane shuffles
+
+struct BestkGeom { int ks_log2, FC, C; };
+
+BestkGeom bestk_geom(const g2k_dims& d, int K) {
+  const int64_t slots = (int64_t)d.S * d.F * d.Nmax;
+  int j = 0;
+  while ((2 << j) <= K && (2 << j) <= kBkMaxSlices && (slots << j) < kBkFill) ++j;
+  int fc = kBkThreads / (d.Nmax << j);
+  if (fc > d.F) fc = d.F;
+  if (fc < 1) fc = 1;
+  BestkGeom g;
+  g.ks_log2 = j;
+  g.FC = fc;
+  g.C = d.F > 0 ? (d.F + fc - 1) / fc : 1;
+  return g;
+}
+
+__device__ __forceinline__ float sgpr(float v) {
+  return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(v)));
+}
+
+__global__ void __launch_bounds__(kBkThreads) g2k_best_of_k_kernel(
+    const float* __restrict__ pred, const float* __restrict__ targets,
+    const int32_t* __restrict__ n_active, const int32_t* __restrict__ n_frames,
+    const uint8_t* __restrict__ ped_mask, const float* __restrict__ head, int F, int Nmax, int FC,
+    int C, int ks_log2, int K, uint32_t seed_lo, uint32_t seed_hi, int shared_targets,
+    float* __restrict__ per_ped, float* __restrict__ best, float* __restrict__ rows) {
+  __shared__ float4 hs[kL];
+  __shared__ float part[kBkThreads / 64][5];
+  const int tid = threadIdx.x;
+  const int s = blockIdx.x / C, c = blockIdx.x - s * C;
+  const int f0 = c * FC;
+  const int fcn = min(FC, F - f0);                         // frames of this chunk (0 when F == 0)
+  const int nact = clampi(n_active[s], 0, Nmax);
+  const int nf = n_frames ? clampi(n_frames[s], 0, F) : F;
+  const int nfc = clampi(nf - f0, 0, fcn);                 // ... of them below n_frames
+  const uint8_t* mask = ped_mask ? ped_mask + (size_t)s * Nmax : nullptr;
+
+  if (tid < kL) {
+    const GaussStep g = gauss_step(head, tid);
+    hs[tid] = make_float4(g.sx, g.sy, g.rho, g.sq);
+  }
+  // non-pairs: zeros in per_ped, pred in best
+  if (per_ped || best) {
+    for (int idx = tid; idx < fcn * Nmax; idx += kBkThreads) {
+      const int fl = idx / Nmax, n = idx - fl * Nmax;
+      const bool pair = fl < nfc && n < nact && (mask ? mask[n] != 0 : true);
+      if (pair) continue;
+      const size_t sf = (size_t)s * F + f0 + fl;
+      if (per_ped) reinterpret_cast<float4*>(per_ped)[sf * Nmax + n] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (best) {
+        const size_t pb = sf * kL2 * Nmax + n;
+#pragma unroll
+        for (int r = 0; r < kL2; ++r) best[pb + (size_t)r * Nmax] = pred[pb + (size_t)r * Nmax];
+      }
+    }
+  }
+  __syncthreads();
+  GaussStep gs[kL];                                        // wave-uniform: scalar registers
+#pragma unroll
+  for (int t = 0; t < kL; ++t) {
+    const float4 v = hs[t];
+    gs[t].sx = sgpr(v.x); gs[t].sy = sgpr(v.y); gs[t].rho = sgpr(v.z); gs[t].sq = sgpr(v.w);
+  }
+
+  const int KS = 1 << ks_log2;
+  const int j = tid & (KS - 1);                            // this lane's slice of the draws
+  const int items = (nfc * nact) << ks_log2;
+  float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int base = 0; base < items; base += kBkThreads) {   // uniform trip count
+    const int p = (base + tid) >> ks_log2;
+    const bool valid = p < nfc * nact;
+    const int fl = valid ? p / nact : 0, n = valid ? p - fl * nact : 0;
+    const bool on = valid && (mask ? mask[n] != 0 : true);
+    const size_t sf = (size_t)s * F + f0 + fl;
+    const size_t pb = sf * kL2 * Nmax + n;
+    const int64_t e0 = (int64_t)(sf * kL) * Nmax + n;      // element of step 0
+    float mu[kL2], tg[kL2];
+    float pa = 0.f, pf = 0.f;                              // ADE / FDE of the mean prediction
+    if (on) {
+      const size_t tf = shared_targets ? (size_t)s : sf;
+      const float2* t2 = reinterpret_cast<const float2*>(targets) + (tf * Nmax + n) * kL;
+#pragma unroll
+      for (int t = 0; t < kL; ++t) {
+        mu[t] = pred[pb + (size_t)t * Nmax];
+        mu[kL + t] = pred[pb + (size_t)(kL + t) * Nmax];
+        const float2 v = t2[t];
+        tg[2 * t] = v.x; tg[2 * t + 1] = v.y;
+      }
+#pragma unroll
+      for (int t = 0; t < kL; ++t) {
+        const float dx = mu[t] - tg[2 * t], dy = mu[kL + t] - tg[2 * t + 1];
+        pf = sqrtf(fmaf(dx, dx, dy * dy));
+        pa += pf;
+      }
+      pa *= 1.0f / 12.0f;
+    } else {
+#pragma unroll
+      for (int r = 0; r < kL2; ++r) { mu[r] = 0.f; tg[r] = 0.f; }
+    }
+    const uint32_t ehi0 = (uint32_t)(e0 >> 32);
+    float bA = __builtin_inff(), bF = __builtin_inff();
+    int kA = 0, kF = 0;
+    // pass 0: this lane's draws (k = j, j + KS, ...) and their running minima,
+    // then the slices' combine; pass 1 (best only): slice 0 makes draw kA
+    // again and stores it.  One loop body for both, so one copy of the draw.
+#pragma nounroll
+    for (int pass = 0; pass < 2; ++pass) {
+      int k = pass ? kA : j;
+      const int kend = pass ? (on && j == 0 ? kA + 1 : kA) : (on ? K : 0);
+      const int kstep = pass ? 1 : KS;
+#pragma nounroll
+      for (; k < kend; k += kstep) {
+        const uint32_t lo = seed_lo + (uint32_t)k;         // (seed + k) mod 2^64
+        const uint32_t hi = seed_hi + (lo < seed_lo ? 1u : 0u);
+        const uint32_t stream0 = gauss_stream(lo, hi, ehi0);
+        float ade = 0.f, dl = 0.f;
+#pragma unroll
+        for (int t = 0; t < kL; ++t) {
+          const int64_t e = e0 + (int64_t)t * Nmax;
+          const uint32_t ehi = (uint32_t)(e >> 32);
+          uint32_t stream = stream0;
+          if (ehi != ehi0) stream = gauss_stream(lo, hi, ehi);   // a pair that straddles 2^32
+          float x, y;
+          gauss_draw(stream, (uint32_t)e, gs[t], mu[t], mu[kL + t], x, y);
+          if (pass) {
+            best[pb + (size_t)t * Nmax] = x;
+            best[pb + (size_t)(kL + t) * Nmax] = y;
+          }
+          const float dx = x - tg[2 * t], dy = y - tg[2 * t + 1];
+          dl = sqrtf(fmaf(dx, dx, dy * dy));
+          ade += dl;
+        }
+        ade *= 1.0f / 12.0f;
+        if (!pass) {
+          if (ade < bA) { bA = ade; kA = k; }              // ascending k, strict: the lowest k stays
+          if (dl < bF) { bF = dl; kF = k; }
+        }
+      }
+      if (pass) break;
+      for (int off = 1; off < KS; off <<= 1) {             // every lane takes part
+        const float oA = __shfl_xor(bA, off), oF = __shfl_xor(bF, off);
+        const int okA = __shfl_xor(kA, off), okF = __shfl_xor(kF, off);
+        if (oA < bA || (oA == bA && okA < kA)) { bA = oA; kA = okA; }
+        if (oF < bF || (oF == bF && okF < kF)) { bF = oF; kF = okF; }
+      }
+      if (!best) break;
+    }
+    if (on && j == 0) {
+      if (per_ped)
+        reinterpret_cast<float4*>(per_ped)[sf * Nmax + n] = make_float4(bA, bF, (float)kA, (float)kF);
+      acc[0] += bA; acc[1] += bF; acc[2] += 1.f; acc[3] += pa; acc[4] += pf;
+    }
+  }
+  // the workgroup's row: lanes by butterfly, waves in order
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {
+    const float v = wave_sum(acc[i]);
+    if ((tid & 63) == 0) part[tid >> 6][i] = v;
+  }
+  __syncthreads();
+  if (tid < 8) {
+    float v = 0.f;
+    if (tid < 5) v = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
+    if (tid == 5) v = (float)K;
+    rows[(size_t)blockIdx.x * 8 + tid] = v;
+  }
+}
+
+// out[s][i] = sum over the scene's C chunk rows, in chunk order
+__global__ void __launch_bounds__(256) g2k_bestk_rows_kernel(const float* __restrict__ rows, int S,
+                                                             int C, int K, float* __restrict__ out) {
+  const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (id >= (int64_t)S * 8) return;
+  const int64_t s = id >> 3;
+  const int i = (int)(id & 7);
+  float v = 0.f;
+  if (i < 5)
+    for (int c = 0; c < C; ++c) v += rows[((size_t)s * C + c) * 8 + i];
+  if (i == 5) v = (float)K;
+  out[id] = v;
+}
+
+}  // namespace
+
+// one row [8] per (scene, chunk); FC >= 1 frame per chunk, so at most F chunks
+int64_t best_of_k_ws_bytes(const g2k_dims* d) {
+  return (int64_t)d->S * (d->F > 1 ? d->F : 1) * 8 * 4;
+}
+
+int best_of_k_launch(const g2k_dims* d, const float* pred, const float* targets,
+                     const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                     const float* head, uint64_t seed, int K, float* per_ped, float* best, float* out,
+                     float* rows, hipStream_t st) {
+  const BestkGeom g = bestk_geom(*d, K);
+  const int64_t wgs = (int64_t)d->S * g.C;
+  if (wgs > 0x7fffffff) return set_err(G2K_EINVAL, "best_of_k: %lld workgroups", (long long)wgs);
+  hipLaunchKernelGGL(g2k_best_of_k_kernel, dim3((unsigned)wgs), dim3(kBkThreads), 0, st, pred, targets,
+                     n_active, n_frames, ped_mask, head, d->F, d->Nmax, g.FC, g.C, g.ks_log2, K,
+                     (uint32_t)seed, (uint32_t)(seed >> 32),
+                     (d->flags & G2K_STEP_TARGETS_SHARED) ? 1 : 0, per_ped, best,
+                     g.C == 1 ? out : rows);
+  int rc = check_launch("g2k_best_of_k_kernel");
+  if (rc || g.C == 1) return rc;
+  hipLaunchKernelGGL(g2k_bestk_rows_kernel, dim3((unsigned)(((int64_t)d->S * 8 + 255) / 256)), dim3(256),
+                     0, st, rows, d->S, g.C, K, out);
+  return check_launch("g2k_bestk_rows_kernel");
+}
+
+}  // namespace g2k

@@ -201,6 +201,51 @@ __device__ __forceinline__ void error_terms(const float* y, const float* tgt, fl
 }
 
 // ---------------------------------------------------------------------------
+// The Gaussian head's counter-based draw, shared by g2k_gauss_sample_kernel
+// (g2k_nll.hip) and g2k_best_of_k_kernel (g2k_bestk.hip) so that a draw made
+// inside the fused evaluation is, bit for bit, the sampler's.  Restated in
+// oracle/g2k_ref.py (gauss_sample).  Every multiply-add is an explicit fmaf:
+// the bits do not depend on what the compiler contracts in either caller.
+//   element e = ((s * F + f) * 12 + t) * Nmax + n  (64 bit)
+//   stream    = pcg(seed_lo ^ pcg(seed_hi ^ (e >> 32)))   (the same for every
+//               element whose high word agrees: hashed once per draw index)
+//   key       = stream ^ (uint32)e;  u1, u2 from pcg(2 key + 1), pcg(2 key + 2)
+//   (e1, e2)  = Box-Muller(u1, u2)
+//   x = mu_x + sigma_x e1,  y = mu_y + sigma_y (rho e1 + sqrt(1 - rho^2) e2)
+// ---------------------------------------------------------------------------
+// 32-bit mix (PCG output permutation of an LCG step)
+__device__ __forceinline__ uint32_t pcg_hash(uint32_t v) {
+  const uint32_t st = v * 747796405u + 2891336453u;
+  const uint32_t w = ((st >> ((st >> 28u) + 4u)) ^ st) * 277803737u;
+  return (w >> 22u) ^ w;
+}
+__device__ __forceinline__ uint32_t gauss_stream(uint32_t seed_lo, uint32_t seed_hi, uint32_t e_hi) {
+  return pcg_hash(seed_lo ^ pcg_hash(seed_hi ^ e_hi));
+}
+// one prediction step's head: sigma_x, sigma_y, rho, sqrt(1 - rho^2)
+struct GaussStep { float sx, sy, rho, sq; };
+__device__ __forceinline__ GaussStep gauss_step(const float* __restrict__ head, int t) {
+  GaussStep g;
+  g.sx = expf(head[t]);
+  g.sy = expf(head[kL + t]);
+  g.rho = tanhf(head[2 * kL + t]);
+  g.sq = sqrtf(fmaf(-g.rho, g.rho, 1.f));
+  return g;
+}
+__device__ __forceinline__ void gauss_draw(uint32_t stream, uint32_t e_lo, const GaussStep& g,
+                                           float mx, float my, float& x, float& y) {
+  const uint32_t key = stream ^ e_lo;
+  const uint32_t h1 = pcg_hash(2u * key + 1u), h2 = pcg_hash(2u * key + 2u);
+  const float u1 = ((float)(h1 >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  const float u2 = ((float)(h2 >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  const float rad = sqrtf(-2.f * logf(u1));
+  const float ang = 6.283185307179586f * u2;
+  const float e1 = rad * cosf(ang), e2 = rad * sinf(ang);
+  x = fmaf(g.sx, e1, mx);
+  y = fmaf(g.sy, fmaf(g.rho, e1, g.sq * e2), my);
+}
+
+// ---------------------------------------------------------------------------
 // LDS polling for the wave-specialised scene kernel.  The loads are inline
 // asm (the compiler may neither hoist nor merge them) and wait for their own
 // data; LDS services one CU's requests in order, so a flag read that sees a
@@ -456,6 +501,13 @@ int nll_launch(const g2k_dims* d, const float* pred, const float* targets, const
                float* dpred, hipStream_t st);
 int gauss_sample_launch(const g2k_dims* d, const float* pred, const float* head, uint64_t seed,
                         float* out, hipStream_t st);
+
+// g2k_bestk.hip
+int64_t best_of_k_ws_bytes(const g2k_dims* d);
+int best_of_k_launch(const g2k_dims* d, const float* pred, const float* targets,
+                     const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                     const float* head, uint64_t seed, int K, float* per_ped, float* best, float* out,
+                     float* rows, hipStream_t st);
 
 // g2k_ops.hip
 int recur_launch(const float* A, float* h, int S, int frames, int D, int H, hipStream_t st);

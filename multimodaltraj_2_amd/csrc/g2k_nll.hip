@@ -25,7 +25,8 @@
 // frames < n_frames).
 // g2k_gauss_sample_kernel: one thread per (s, f, t, n): x = mu_x + sigma_x e1,
 // y = mu_y + sigma_y (rho e1 + sqrt(c) e2), (e1, e2) by Box-Muller from a
-// counter-based hash of (seed, element) — reproducible, restated in the oracle.
+// counter-based hash of (seed, element) — reproducible, restated in the oracle
+// (gauss_draw, g2k_common.h: the same draw g2k_bestk.hip makes in registers).
 #include "g2k_common.h"
 
 namespace g2k {
@@ -94,34 +95,23 @@ __global__ void __launch_bounds__(kNllThreads) g2k_nll_kernel(
   }
 }
 
-// 32-bit mix (PCG output permutation of an LCG step): the sampler's
-// counter-based uniform source; restated in oracle/g2k_ref.py (gauss_sample)
-__device__ __forceinline__ uint32_t pcg_hash(uint32_t v) {
-  const uint32_t st = v * 747796405u + 2891336453u;
-  const uint32_t w = ((st >> ((st >> 28u) + 4u)) ^ st) * 277803737u;
-  return (w >> 22u) ^ w;
-}
-
 __global__ void __launch_bounds__(256) g2k_gauss_sample_kernel(
     const float* __restrict__ pred, const float* __restrict__ head, int64_t total, int Nmax,
     uint32_t seed_lo, uint32_t seed_hi, float* __restrict__ out) {
-  // element e = ((s * F + f) * 12 + t) * Nmax + n
+  // element e = ((s * F + f) * 12 + t) * Nmax + n; the draw itself is
+  // gauss_draw (g2k_common.h), shared with the best-of-K evaluation
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= total) return;
   const int n = (int)(e % Nmax);
   const int64_t sft = e / Nmax;
   const int t = (int)(sft % kL);
   const int64_t sf = sft / kL;
-  const uint32_t key = pcg_hash(seed_lo ^ pcg_hash(seed_hi ^ (uint32_t)(e >> 32))) ^ (uint32_t)e;
-  const uint32_t h1 = pcg_hash(2u * key + 1u), h2 = pcg_hash(2u * key + 2u);
-  const float u1 = ((float)(h1 >> 8) + 0.5f) * (1.0f / 16777216.0f);
-  const float u2 = ((float)(h2 >> 8) + 0.5f) * (1.0f / 16777216.0f);
-  const float rad = sqrtf(-2.f * logf(u1));
-  const float e1 = rad * cosf(6.283185307179586f * u2), e2 = rad * sinf(6.283185307179586f * u2);
-  const float sx = expf(head[t]), sy = expf(head[kL + t]), rho = tanhf(head[2 * kL + t]);
   const size_t px = (size_t)(sf * kL2 + t) * Nmax + n, py = (size_t)(sf * kL2 + kL + t) * Nmax + n;
-  out[px] = pred[px] + sx * e1;
-  out[py] = pred[py] + sy * (rho * e1 + sqrtf(1.f - rho * rho) * e2);
+  float x, y;
+  gauss_draw(gauss_stream(seed_lo, seed_hi, (uint32_t)(e >> 32)), (uint32_t)e, gauss_step(head, t),
+             pred[px], pred[py], x, y);
+  out[px] = x;
+  out[py] = y;
 }
 
 }  // namespace

@@ -1,0 +1,105 @@
+"""Multimodal evaluation: best-of-K sampling on the left-out dataset
+(minADE_K / minFDE_K, the usual figure of a probabilistic predictor on
+ETH/UCY at K = 20).
+
+  python -m multimodaltraj_2_amd.evaluate --data_root D --save_dir DIR \
+      --leaveDataset l --num_samples 20 [--sample_seed N]
+
+Every distinct scene of dataset l (realdata.plan_scenes: sample.py's scene per
+frame pointer, as --mode train takes them from the training datasets) goes
+through ONE fused step (g2k_step_fused_f32, stride 0, one frame: a real
+scene's prediction is the same in every frame of its loop, so each (scene,
+pedestrian) counts once, not once per frame) and ONE g2k_best_of_k_f32 launch
+over its predictions: K draws of the Gaussian head around each prediction,
+the smallest ADE and FDE per pedestrian, no draw ever in memory
+(csrc/g2k_bestk.hip).  The head is the checkpoint's (``nll_head/head``, which
+--mode train --loss nll learns) or, for parameters without one, a constant
+exp(--head_log_sigma) per step.  The build's: the reference has no
+probabilistic head, so these figures have no
+reference counterpart.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import checkpoint
+from . import frame_step as fs
+from . import realdata as rd
+from .nll import GaussianHead
+
+FIGURES = ("ade", "fde", "min_ade", "min_fde")
+
+
+def left_out_plan(args, nmax):
+    """The RealPlan of every distinct scene (2 <= P <= nmax) of the left-out
+    dataset; FileNotFoundError when it is not under --data_root (5,
+    town_center.csv, is absent from the reference's data)."""
+    l = int(args.leaveDataset)
+    names = [n for n, i in rd.DATASETS.items() if i == l]
+    if not names:
+        raise FileNotFoundError(f"dataset {l} is not among the shipped datasets {rd.DATASETS}")
+    raw = rd.load_raw(names, args.data_root)
+    n = rd.count_scenes(raw, nmax)
+    if n == 0:
+        raise ValueError(f"dataset {l}: no scene with 2 <= P <= {nmax}")
+    return rd.plan_scenes(n, raw, nmax=nmax)
+
+
+def evaluate_best_of_k(args, params, device, log=print, keep=None):
+    """--num_samples K on --leaveDataset with ``params`` (a G2KParams on
+    ``device``).  Logs and returns {scenes, pairs, K, ade, fde, min_ade,
+    min_fde} (errors per (scene, pedestrian) pair; ade / fde: the mean
+    prediction's).  ``keep`` (a dict) receives the plan, the predictions, the
+    head and the kernel's outputs for a caller that checks them."""
+    from .train import context_G
+    K = int(args.num_samples)
+    if K < 1:
+        raise ValueError("--num_samples K must be >= 1")
+    plan = left_out_plan(args, params.nmax)
+    S = plan.S
+    t = plan.to_device(device, F=1)
+    G = torch.from_numpy(context_G(args.seed, S)).to(device)
+    h0 = torch.zeros((S, fs.HIDDEN_LEN, args.rnn_size), device=device)
+    one = torch.ones(S, dtype=torch.int32, device=device)
+    out = fs.step_fused(params, t["pos"], t["vislet"], G, t["targets"], t["n_active"], h0,
+                        n_frames=one, ped_mask=t["ped_mask"], stride=0, lam=args.lambda_param)
+    if params.head is not None:
+        gh = GaussianHead(device=device)
+        gh.head = params.head.contiguous()
+        log("best-of-K: the parameters' learned head (nll_head/head)")
+    else:
+        gh = GaussianHead(log_sigma=args.head_log_sigma, device=device)
+        log(f"best-of-K: no head in the parameters, constant log sigma {args.head_log_sigma}")
+    bk = gh.best_of_k(out.pred, t["targets"], t["n_active"], K, seed=args.sample_seed, n_frames=one,
+                      ped_mask=t["ped_mask"], want_per_ped=False)
+    res = dict(scenes=S, pairs=bk.pairs, K=K, ade=bk.ade, fde=bk.fde, min_ade=bk.min_ade,
+               min_fde=bk.min_fde)
+    log(f"best-of-{K} on dataset {args.leaveDataset}: {S} scenes, {res['pairs']} pairs, "
+        f"ADE {res['ade']:.6g} FDE {res['fde']:.6g} minADE_{K} {res['min_ade']:.6g} "
+        f"minFDE_{K} {res['min_fde']:.6g}")
+    if keep is not None:
+        keep.update(plan=plan, pred=out.pred, head=gh.head, out=bk, n_frames=np.ones(S, np.int32))
+    return res
+
+
+def main(argv=None, log=print):
+    from .argParser import ArgsParser
+    args = ArgsParser().parser.parse_args(argv)
+    if args.num_samples < 1:
+        raise SystemExit("evaluate: --num_samples K (>= 1) is required")
+    prefix = checkpoint.read_state(args.save_dir) if args.save_dir else None
+    if not prefix:
+        raise SystemExit(f"evaluate: no checkpoint state under --save_dir {args.save_dir!r}")
+    device = torch.device(args.device)
+    params = checkpoint.load_params(prefix, device=device)
+    log(f"evaluate: {prefix} (Nmax {params.nmax})")
+    try:
+        return evaluate_best_of_k(args, params, device, log=log)
+    except FileNotFoundError as exc:
+        log(f"evaluation dataset {args.leaveDataset}: {exc}")
+        return None
+
+
+if __name__ == '__main__':
+    main()

@@ -8,15 +8,54 @@ sigma_y, atanh rho per prediction step) around the model's predictions
 (pred_path_band as the fused step writes it: [S, F, 2L, Nmax]); ``nll``
 returns the summed loss, the pair count, d nll / d head and (optionally)
 d nll / d pred; ``sample`` draws one reproducible trajectory per
-(step, pedestrian)."""
+(step, pedestrian); ``best_of_k`` evaluates K such draws against the targets
+in one launch (minADE_K / minFDE_K, csrc/g2k_bestk.hip)."""
 from __future__ import annotations
 
 import ctypes
+from dataclasses import dataclass
 
 import torch
 
 from . import _lib
 from .frame_step import OBS_LEN, PRED_LEN, _check_dev, _ptr, _stream
+
+
+@dataclass
+class BestOfK:
+    """``GaussianHead.best_of_k``'s outputs (include/g2k_hip.h)."""
+    sums: torch.Tensor              # [S, 8] {sum minADE, sum minFDE, pairs, sum ADE, sum FDE, K, 0, 0}
+    per_ped: torch.Tensor | None    # [S, F, Nmax, 4] {minADE, minFDE, kA, kF}; zeros for non-pairs
+    best: torch.Tensor | None       # [S, F, 2L, Nmax] draw kA for pairs, pred elsewhere
+
+    def totals(self):
+        """The sums over all scenes, on the host (one read, float64)."""
+        return self.sums.double().sum(dim=0).tolist()
+
+    def _mean(self, i):
+        t = self.totals()
+        return t[i] / t[2] if t[2] > 0 else float("nan")
+
+    @property
+    def pairs(self) -> int:
+        return int(self.totals()[2])
+
+    @property
+    def min_ade(self) -> float:
+        return self._mean(0)
+
+    @property
+    def min_fde(self) -> float:
+        return self._mean(1)
+
+    @property
+    def ade(self) -> float:
+        """The mean prediction's ADE (no sampling) over the same pairs."""
+        return self._mean(3)
+
+    @property
+    def fde(self) -> float:
+        return self._mean(4)
 
 
 class GaussianHead:
@@ -53,6 +92,49 @@ class GaussianHead:
                              _ptr(ws), ws.numel(), _stream(stream))
         _lib.check("g2k_nll_f32", rc)
         return out[3 * PRED_LEN], out[3 * PRED_LEN + 1], out[:3 * PRED_LEN].view(3, PRED_LEN), dpred
+
+    def best_of_k(self, pred, targets, n_active, k, seed=0, *, n_frames=None, ped_mask=None,
+                  targets_shared=False, want_per_ped=True, want_best=False, stream=None):
+        """Best-of-K sampling evaluation in one launch (g2k_best_of_k_f32): of
+        the K draws ``sample(pred, seed + i)``, i < k, each pair's smallest ADE
+        and FDE and the draws that attain them -> BestOfK."""
+        lib = _lib.load()
+        dev = pred.device
+        d = self._dims(pred)
+        S, F, Nmax = d.S, d.F, d.Nmax
+        if targets_shared:
+            d.flags = _lib.STEP_TARGETS_SHARED
+        _check_dev("pred", pred, dev, torch.float32)
+        _check_dev("head", self.head, dev, torch.float32)
+        if tuple(n_active.shape) != (S,):
+            raise ValueError("n_active must be [S]")
+        _check_dev("n_active", n_active, dev, torch.int32)
+        tshape = (S, 1 if targets_shared else F, Nmax, PRED_LEN, 2)
+        if tuple(targets.shape) != tshape:
+            raise ValueError(f"targets must be {list(tshape)}")
+        _check_dev("targets", targets, dev, torch.float32)
+        if n_frames is not None:
+            if tuple(n_frames.shape) != (S,):
+                raise ValueError("n_frames must be [S]")
+            _check_dev("n_frames", n_frames, dev, torch.int32)
+        if ped_mask is not None:
+            if tuple(ped_mask.shape) != (S, Nmax):
+                raise ValueError("ped_mask must be [S, Nmax]")
+            _check_dev("ped_mask", ped_mask, dev, torch.uint8)
+        k = int(k)
+        if not 1 <= k <= 4096:
+            raise ValueError(f"k = {k}: 1..4096")
+        sums = torch.empty((S, 8), dtype=torch.float32, device=dev)
+        per_ped = torch.empty((S, F, Nmax, 4), dtype=torch.float32, device=dev) if want_per_ped else None
+        best = torch.empty_like(pred) if want_best else None
+        ws = torch.empty(max(1, int(lib.g2k_best_of_k_workspace_bytes(ctypes.byref(d)))),
+                         dtype=torch.uint8, device=dev)
+        rc = lib.g2k_best_of_k_f32(ctypes.byref(d), _ptr(pred), _ptr(targets), _ptr(n_active),
+                                   _ptr(n_frames), _ptr(ped_mask), _ptr(self.head),
+                                   ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), k, _ptr(per_ped),
+                                   _ptr(best), _ptr(sums), _ptr(ws), ws.numel(), _stream(stream))
+        _lib.check("g2k_best_of_k_f32", rc)
+        return BestOfK(sums=sums, per_ped=per_ped, best=best)
 
     def sample(self, pred, seed=0, stream=None):
         """One draw around pred [S, F, 2L, Nmax] (same layout out)."""

@@ -43,7 +43,9 @@
   datasets), --train_batch scenes per global step, each rank taking its
   contiguous shard (dist.shard_scenes) and ONE all-reduce of the flat gradient
   per step (RCCL under torchrun with the nccl backend), then the same update on
-  every rank.
+  every rank.  With --num_samples K > 0, rank 0 then evaluates the trained
+  parameters on the left-out dataset by best-of-K sampling (evaluate.py:
+  minADE_K / minFDE_K, one g2k_best_of_k_f32 launch).
 
 The model weights are one seeded N(0, 1) draw (quirk Q15: the reference
 re-draws them every batch), padded to Nmax (8 for the node slice).
@@ -384,7 +386,8 @@ def run_train_mode(args, device, log=print):
     plan = rd.plan_scenes(args.train_scenes or rd.count_scenes(raw, args.n_max), raw,
                           nmax=args.n_max or None)
     params, losses = train_mode(args, plan, device, rank=rank, world=world, group=group, log=log)
-    if rank == 0 and args.save_dir:
+    num_samples = getattr(args, "num_samples", 0)
+    if rank == 0 and (args.save_dir or num_samples > 0):
         flat = torch.from_numpy(params.astype(np.float32))
         from .train_step import GRAD_ORDER
         keys = GRAD_ORDER + (("head",) if args.loss == "nll" else ())
@@ -395,8 +398,16 @@ def run_train_mode(args, device, log=print):
             n = int(np.prod(shapes[k]))
             views[k] = flat[o:o + n].view(shapes[k])
             o += n
-        checkpoint.save_params(os.path.join(args.save_dir, "g2k_MPC_model_train_mode.ckpt-"
-                                            f"{args.num_epochs}"), fs.G2KParams(**views))
+        trained = fs.G2KParams(**views)
+        if args.save_dir:
+            checkpoint.save_params(os.path.join(args.save_dir, "g2k_MPC_model_train_mode.ckpt-"
+                                                f"{args.num_epochs}"), trained)
+        if num_samples > 0:              # --num_samples K: best-of-K on the left-out dataset
+            from .evaluate import evaluate_best_of_k
+            try:
+                evaluate_best_of_k(args, trained.to(device), device, log=log)
+            except FileNotFoundError as exc:
+                log(f"evaluation dataset {args.leaveDataset}: {exc}")
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
