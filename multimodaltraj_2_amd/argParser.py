@@ -2,7 +2,7 @@
 the build's own: --data_root (Q8), --device, --mode,
 --world_size, --n_max, --train_batch, --train_scenes, --valid_from_seed,
 --log_dir, --save_dir, --seed, --use_grid_lstm, --loss, --num_samples,
---sample_seed, --head_log_sigma."""
+--sample_seed, --head_log_sigma, --collision_radius."""
 import argparse
 
 
@@ -55,6 +55,11 @@ class ArgsParser:
     parser.add_argument('--head_log_sigma', type=float, default=0.0,
                         help="--num_samples: log sigma of the head when the parameters hold none "
                              "(an L2-trained checkpoint)")
+    parser.add_argument('--collision_radius', type=float, default=0.0,
+                        help='--num_samples: also report the joint best-of-K figures (JADE_K / '
+                             'JFDE_K) and the collision rates: two pedestrians collide when they '
+                             'come closer than this at any predicted step, in the units of the '
+                             "dataset's position columns (0: off)")
     parser.add_argument('--train_scenes', type=int, default=0,
                         help='--mode train: distinct scenes used (0: all of the fold)')
     parser.add_argument('--valid_from_seed', type=int, default=0,

@@ -202,8 +202,8 @@ __device__ __forceinline__ void error_terms(const float* y, const float* tgt, fl
 
 // ---------------------------------------------------------------------------
 // The Gaussian head's counter-based draw, shared by g2k_gauss_sample_kernel
-// (g2k_nll.hip) and g2k_best_of_k_kernel (g2k_bestk.hip) so that a draw made
-// inside the fused evaluation is, bit for bit, the sampler's.  Restated in
+// (g2k_nll.hip), g2k_best_of_k_kernel (g2k_bestk.hip) and g2k_joint_kernel
+// (g2k_joint.hip) so that a draw made inside a fused evaluation is, bit for bit, the sampler's.  Restated in
 // oracle/g2k_ref.py (gauss_sample).  Every multiply-add is an explicit fmaf:
 // the bits do not depend on what the compiler contracts in either caller.
 //   element e = ((s * F + f) * 12 + t) * Nmax + n  (64 bit)
@@ -508,6 +508,14 @@ int best_of_k_launch(const g2k_dims* d, const float* pred, const float* targets,
                      const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
                      const float* head, uint64_t seed, int K, float* per_ped, float* best, float* out,
                      float* rows, hipStream_t st);
+
+// g2k_joint.hip
+int64_t joint_eval_ws_bytes(const g2k_dims* d);
+int joint_eval_launch(const g2k_dims* d, const float* pred, const float* targets,
+                      const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                      const float* head, uint64_t seed, int K, float radius, float* per_frame_f,
+                      int32_t* per_frame_i, float* sums_f, int64_t* sums_i, int32_t* rows,
+                      hipStream_t st);
 
 // g2k_ops.hip
 int recur_launch(const float* A, float* h, int S, int frames, int D, int H, hipStream_t st);

@@ -12,7 +12,17 @@ scene's prediction is the same in every frame of its loop, so each (scene,
 pedestrian) counts once, not once per frame) and ONE g2k_best_of_k_f32 launch
 over its predictions: K draws of the Gaussian head around each prediction,
 the smallest ADE and FDE per pedestrian, no draw ever in memory
-(csrc/g2k_bestk.hip).  The head is the checkpoint's (``nll_head/head``, which
+(csrc/g2k_bestk.hip).  With --collision_radius R > 0 one g2k_joint_eval_f32
+launch (csrc/g2k_joint.hip) follows on the same predictions, head and seed:
+the K draws taken as joint samples of a scene (JADE_K / JFDE_K: one k for all
+pedestrians of the scene, so never below minADE_K / minFDE_K) and the share of
+pedestrian couples that come closer than R at any of the 12 predicted steps —
+in the K samples, in the mean prediction, in each scene's best joint sample
+and in the ground truth.  R is in the units realdata.plan_scenes hands the
+kernels: the position columns of the dataset's CSV as they are, neither
+normalised nor shifted — for the UCY sets (zara01, zara02, ucy_univ) world
+coordinates spanning about -9..5 by -3..3, for eth_hotel image coordinates
+normalised to 0..1.  The head is the checkpoint's (``nll_head/head``, which
 --mode train --loss nll learns) or, for parameters without one, a constant
 exp(--head_log_sigma) per step.  The build's: the reference has no
 probabilistic head, so these figures have no
@@ -29,6 +39,8 @@ from . import realdata as rd
 from .nll import GaussianHead
 
 FIGURES = ("ade", "fde", "min_ade", "min_fde")
+JOINT_FIGURES = ("jade", "jfde", "ped_pairs", "collision_rate", "collision_rate_pred",
+                 "collision_rate_best", "collision_rate_gt")
 
 
 def left_out_plan(args, nmax):
@@ -50,8 +62,10 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
     """--num_samples K on --leaveDataset with ``params`` (a G2KParams on
     ``device``).  Logs and returns {scenes, pairs, K, ade, fde, min_ade,
     min_fde} (errors per (scene, pedestrian) pair; ade / fde: the mean
-    prediction's).  ``keep`` (a dict) receives the plan, the predictions, the
-    head and the kernel's outputs for a caller that checks them."""
+    prediction's), with --collision_radius R > 0 also JOINT_FIGURES from one
+    joint_eval launch and a second log line.  ``keep`` (a dict) receives the
+    plan, the predictions, the head and the kernels' outputs for a caller that
+    checks them."""
     from .train import context_G
     K = int(args.num_samples)
     if K < 1:
@@ -78,8 +92,20 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
     log(f"best-of-{K} on dataset {args.leaveDataset}: {S} scenes, {res['pairs']} pairs, "
         f"ADE {res['ade']:.6g} FDE {res['fde']:.6g} minADE_{K} {res['min_ade']:.6g} "
         f"minFDE_{K} {res['min_fde']:.6g}")
+    joint = None
+    radius = float(getattr(args, "collision_radius", 0.0) or 0.0)
+    if radius > 0:
+        joint = gh.joint_eval(out.pred, t["targets"], t["n_active"], K, radius, seed=args.sample_seed,
+                              n_frames=one, ped_mask=t["ped_mask"], want_per_frame=keep is not None)
+        res.update({k: getattr(joint, k) for k in JOINT_FIGURES})
+        log(f"joint best-of-{K} on dataset {args.leaveDataset}: radius {radius:g}, "
+            f"{res['ped_pairs']} couples, JADE_{K} {res['jade']:.6g} JFDE_{K} {res['jfde']:.6g} "
+            f"collision rate: samples {res['collision_rate']:.6g} mean {res['collision_rate_pred']:.6g} "
+            f"best joint sample {res['collision_rate_best']:.6g} "
+            f"ground truth {res['collision_rate_gt']:.6g}")
     if keep is not None:
-        keep.update(plan=plan, pred=out.pred, head=gh.head, out=bk, n_frames=np.ones(S, np.int32))
+        keep.update(plan=plan, pred=out.pred, head=gh.head, out=bk, n_frames=np.ones(S, np.int32),
+                    joint=joint)
     return res
 
 

@@ -9,7 +9,9 @@ sigma_y, atanh rho per prediction step) around the model's predictions
 returns the summed loss, the pair count, d nll / d head and (optionally)
 d nll / d pred; ``sample`` draws one reproducible trajectory per
 (step, pedestrian); ``best_of_k`` evaluates K such draws against the targets
-in one launch (minADE_K / minFDE_K, csrc/g2k_bestk.hip)."""
+in one launch (minADE_K / minFDE_K, csrc/g2k_bestk.hip); ``joint_eval``
+scores the same K draws as JOINT samples of a scene-frame (JADE_K / JFDE_K)
+and counts collisions between the pedestrians (csrc/g2k_joint.hip)."""
 from __future__ import annotations
 
 import ctypes
@@ -56,6 +58,67 @@ class BestOfK:
     @property
     def fde(self) -> float:
         return self._mean(4)
+
+
+@dataclass
+class JointEval:
+    """``GaussianHead.joint_eval``'s outputs (include/g2k_hip.h).  Every
+    property is one host read (float64 / int); a rate whose denominator is 0
+    is NaN."""
+    sums_f: torch.Tensor                # [S, 4] {sum_f P minJADE, sum_f P minJFDE, K, 0}
+    sums_i: torch.Tensor                # [S, 6] int64: sum_f of the per_frame_i columns
+    per_frame_f: torch.Tensor | None    # [S, F, 4] {minJADE, minJFDE, kJA, kJF}
+    per_frame_i: torch.Tensor | None    # [S, F, 6] int32 {P, PP, col_pred, col_gt, sum_k col_k, col_best}
+    k: int = 0
+    radius: float = 0.0
+
+    def _f(self, i):
+        return float(self.sums_f[:, i].double().sum().item())
+
+    def _i(self, i):
+        return int(self.sums_i[:, i].sum().item())
+
+    def _rate(self, i, scale=1):
+        den = self._i(1) * scale
+        return self._i(i) / den if den > 0 else float("nan")
+
+    @property
+    def pairs(self) -> int:
+        """(scene-frame, member) pairs: the denominator of ADE / minADE_K too."""
+        return self._i(0)
+
+    @property
+    def ped_pairs(self) -> int:
+        """Unordered member couples, summed over the scene-frames."""
+        return self._i(1)
+
+    @property
+    def jade(self) -> float:
+        p = self.pairs
+        return self._f(0) / p if p > 0 else float("nan")
+
+    @property
+    def jfde(self) -> float:
+        p = self.pairs
+        return self._f(1) / p if p > 0 else float("nan")
+
+    @property
+    def collision_rate(self) -> float:
+        """Of the K samples: colliding couples per couple and draw."""
+        return self._rate(4, self.k)
+
+    @property
+    def collision_rate_pred(self) -> float:
+        return self._rate(2)
+
+    @property
+    def collision_rate_best(self) -> float:
+        """Of each scene-frame's best joint sample (draw kJA)."""
+        return self._rate(5)
+
+    @property
+    def collision_rate_gt(self) -> float:
+        return self._rate(3)
 
 
 class GaussianHead:
@@ -135,6 +198,59 @@ class GaussianHead:
                                    _ptr(best), _ptr(sums), _ptr(ws), ws.numel(), _stream(stream))
         _lib.check("g2k_best_of_k_f32", rc)
         return BestOfK(sums=sums, per_ped=per_ped, best=best)
+
+    def joint_eval(self, pred, targets, n_active, k, radius, seed=0, *, n_frames=None, ped_mask=None,
+                   targets_shared=False, want_per_frame=True, stream=None):
+        """Joint best-of-K evaluation in one launch (g2k_joint_eval_f32): draw
+        i < k of EVERY member of a scene-frame is ``sample(pred, seed + i)``;
+        per scene-frame the smallest mean ADE / FDE over the members (JADE_K /
+        JFDE_K) and the couples that come closer than ``radius`` at any of the
+        12 predicted steps, in the draws, the mean prediction and the targets
+        -> JointEval."""
+        import math
+        lib = _lib.load()
+        dev = pred.device
+        d = self._dims(pred)
+        S, F, Nmax = d.S, d.F, d.Nmax
+        if targets_shared:
+            d.flags = _lib.STEP_TARGETS_SHARED
+        _check_dev("pred", pred, dev, torch.float32)
+        _check_dev("head", self.head, dev, torch.float32)
+        if tuple(n_active.shape) != (S,):
+            raise ValueError("n_active must be [S]")
+        _check_dev("n_active", n_active, dev, torch.int32)
+        tshape = (S, 1 if targets_shared else F, Nmax, PRED_LEN, 2)
+        if tuple(targets.shape) != tshape:
+            raise ValueError(f"targets must be {list(tshape)}")
+        _check_dev("targets", targets, dev, torch.float32)
+        if n_frames is not None:
+            if tuple(n_frames.shape) != (S,):
+                raise ValueError("n_frames must be [S]")
+            _check_dev("n_frames", n_frames, dev, torch.int32)
+        if ped_mask is not None:
+            if tuple(ped_mask.shape) != (S, Nmax):
+                raise ValueError("ped_mask must be [S, Nmax]")
+            _check_dev("ped_mask", ped_mask, dev, torch.uint8)
+        k = int(k)
+        if not 1 <= k <= 4096:
+            raise ValueError(f"k = {k}: 1..4096")
+        radius = float(radius)
+        if not (math.isfinite(radius) and radius >= 0.0):
+            raise ValueError(f"radius = {radius}: finite and >= 0")
+        sums_f = torch.empty((S, 4), dtype=torch.float32, device=dev)
+        sums_i = torch.empty((S, 6), dtype=torch.int64, device=dev)
+        pf = torch.empty((S, F, 4), dtype=torch.float32, device=dev) if want_per_frame else None
+        pi = torch.empty((S, F, 6), dtype=torch.int32, device=dev) if want_per_frame else None
+        ws = torch.empty(max(1, int(lib.g2k_joint_eval_workspace_bytes(ctypes.byref(d)))),
+                         dtype=torch.uint8, device=dev)
+        rc = lib.g2k_joint_eval_f32(ctypes.byref(d), _ptr(pred), _ptr(targets), _ptr(n_active),
+                                    _ptr(n_frames), _ptr(ped_mask), _ptr(self.head),
+                                    ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), k,
+                                    ctypes.c_float(radius), _ptr(pf), _ptr(pi), _ptr(sums_f),
+                                    _ptr(sums_i), _ptr(ws), ws.numel(), _stream(stream))
+        _lib.check("g2k_joint_eval_f32", rc)
+        return JointEval(sums_f=sums_f, sums_i=sums_i, per_frame_f=pf, per_frame_i=pi, k=k,
+                         radius=radius)
 
     def sample(self, pred, seed=0, stream=None):
         """One draw around pred [S, F, 2L, Nmax] (same layout out)."""

@@ -45,7 +45,9 @@
   per step (RCCL under torchrun with the nccl backend), then the same update on
   every rank.  With --num_samples K > 0, rank 0 then evaluates the trained
   parameters on the left-out dataset by best-of-K sampling (evaluate.py:
-  minADE_K / minFDE_K, one g2k_best_of_k_f32 launch).
+  minADE_K / minFDE_K, one g2k_best_of_k_f32 launch; with --collision_radius
+  R > 0 also JADE_K / JFDE_K and the collision rates, one g2k_joint_eval_f32
+  launch).
 
 The model weights are one seeded N(0, 1) draw (quirk Q15: the reference
 re-draws them every batch), padded to Nmax (8 for the node slice).
