@@ -240,7 +240,11 @@ int g2k_frame_recurrence_f32(const g2k_dims* d, const float* A, float* h,
  *   variant 0: validation sums (train.py:640-674) -> out [S, 8] as metrics above
  *   variant 1: get_mean_error (sample.py:21-82) -> out [S, 8] =
  *              {ADE, FDE, counter, 0...}; pred/targets are [S, 2L, Nmax] /
- *              [S, Nmax, L, 2] with F = 1 and obs_length = d->T.
+ *              [S, Nmax, L, 2] with F = 1 and obs_length = d->T.  A scene
+ *              with n_active = 0 gets {0, 0, 0, 0...} (the reference raises
+ *              there: nothing to average).
+ * Every element of out is written; only columns < n_active, frames < n_frames
+ * of pred / targets are read.
  * Replaces: the numpy error loops train.py:636-674 and sample.py:21-82.
  *   pred [S, F, 2L, Nmax]; targets [S, F, Nmax, L, 2]; n_active [S];
  *   n_frames [S] or NULL; ped_mask [S, Nmax] or NULL.
@@ -394,8 +398,11 @@ int g2k_step_grad_update_f32(const g2k_dims* d, const g2k_weights* w, const floa
  * g2k_nll_f32: out [38] = {d nll / d head (36, head order), nll summed over
  *   frames < n_frames, active masked pedestrians and the 12 steps, count of
  *   (frame, pedestrian) pairs}, fixed reduction order; dpred (or NULL) =
- *   d nll / d pred for those pairs, zero for the other active columns of
- *   frames < n_frames.  workspace >= g2k_nll_workspace_bytes(d).
+ *   d nll / d pred for those pairs, exactly zero for the masked-out active
+ *   columns of frames < n_frames; columns >= n_active and frames >= n_frames
+ *   of dpred are NOT written (a caller that wants zeros there zero-fills
+ *   dpred first, as GaussianHead.nll does).  workspace >=
+ *   g2k_nll_workspace_bytes(d).
  * g2k_gauss_sample_f32: out [S, F, 2L, Nmax] = one draw per (step, pedestrian)
  *   from the head's Gaussian around pred (Box-Muller over a counter-based
  *   hash of seed and the element index: reproducible).  Reads d->S, F, Nmax.

@@ -364,7 +364,8 @@ __global__ void __launch_bounds__(64) g2k_errors_v1_kernel(ErrArgs a) {
   fsum = wave_sum(fsum);
   if (lane < 8) {
     float v = 0.f;
-    if (lane == 0) v = ade / (float)(kL - obs);
+    // no pedestrians: the reference raises (np.stack of an empty list); {0, 0, 0} here
+    if (lane == 0) v = nact > 0 ? ade / (float)(kL - obs) : 0.f;
     else if (lane == 1) v = nact > 0 ? fsum / (float)nact / (float)nact : 0.f;
     else if (lane == 2) v = counter;
     a.out[(size_t)s * 8 + lane] = v;
