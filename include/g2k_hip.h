@@ -472,6 +472,40 @@ int g2k_joint_eval_f32(const g2k_dims* d, const float* pred, const float* target
                        int32_t* per_frame_i, float* sums_f, int64_t* sums_i, void* workspace,
                        int64_t workspace_bytes, void* stream);
 
+/*
+ * Calibration of the head (added after ABI 11; detect by symbol;
+ * csrc/g2k_calib.hip): the per-step residual moments, their closed-form
+ * maximum-likelihood head, and the coverage / NLL of a given head, one pass
+ * over pred and targets.  Inputs and pairs as g2k_best_of_k_f32; head [3][12]
+ * or NULL; r2 [n_levels] doubles on the device (8-byte aligned), n_levels in
+ * 0..32.  For a pair and step t, in double:
+ *   dx = target_x - pred_x, dy = target_y - pred_y
+ *   a = dx / sigma_x, b = dy / sigma_y, c = 1 - rho^2
+ *   q = (a^2 + b^2 - 2 rho a b) / c   (chi^2(2) under a calibrated head)
+ *   nll = log 2 pi + log sigma_x + log sigma_y + 1/2 log c + q / 2
+ *   stats [12][8] (double) = {pairs, sum dx, sum dy, sum dx^2, sum dy^2,
+ *     sum dx dy, sum nll_t, sum q_t}; columns 6, 7 exactly 0 when head is NULL
+ *   inside [12][n_levels] (int64) or NULL: pairs with q_t <= r2[l]
+ *   fit [3][12] (f32) or NULL: the head that minimises the NLL over the pairs,
+ *     log sigma_x = 1/2 ln max(sum dx^2 / n, 1e-12), log sigma_y likewise,
+ *     atanh rho with rho = sum dx dy / sqrt(sum dx^2 sum dy^2) clamped to
+ *     +-(1 - 1e-6), 0 when either sum is 0; zeros for a step with n = 0
+ * Every element of stats, inside and fit is written on every call with
+ * S >= 1 (zeros when there is no pair); columns >= n_active, frames >=
+ * n_frames and masked columns of pred / targets are never read.  head == NULL
+ * requires n_levels == 0 and inside == NULL.  Nmax in 1..256, S F < 2^31,
+ * workspace (8-byte aligned) >= g2k_head_stats_workspace_bytes(d, n_levels),
+ * which is 0 when one workgroup covers the launch (else G2K_EINVAL before any
+ * launch); S = 0 is a no-op.  Asynchronous, no allocation, capturable; fixed
+ * summation order, no atomics: repeated calls are bit-identical.
+ */
+int64_t g2k_head_stats_workspace_bytes(const g2k_dims* d, int32_t n_levels);
+int g2k_head_stats_f32(const g2k_dims* d, const float* pred, const float* targets,
+                       const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                       const float* head, const double* r2, int32_t n_levels, double* stats,
+                       int64_t* inside, float* fit, void* workspace, int64_t workspace_bytes,
+                       void* stream);
+
 int64_t g2k_context_conv_workspace_bytes(int32_t Hh, int32_t Ww, int32_t D);
 int g2k_context_conv_f32(const float* img, int32_t Hh, int32_t Ww, int32_t C, const float* filt,
                          int32_t D, float lambda, float* out, float* G, void* workspace,

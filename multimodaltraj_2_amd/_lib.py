@@ -82,6 +82,9 @@ SYMBOLS = {
     "g2k_joint_eval_f32": (c_int, [ctypes.POINTER(G2KDims), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                    ctypes.c_uint64, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64,
                                    c_vp]),
+    "g2k_head_stats_workspace_bytes": (c_i64, [ctypes.POINTER(G2KDims), c_i32]),
+    "g2k_head_stats_f32": (c_int, [ctypes.POINTER(G2KDims), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                   c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "g2k_step_grad_update_f32": (c_int, [ctypes.POINTER(G2KDims), ctypes.POINTER(G2KWeights),
                                          c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp,
                                          c_vp, c_i64, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp]),

@@ -2,7 +2,8 @@
 the build's own: --data_root (Q8), --device, --mode,
 --world_size, --n_max, --train_batch, --train_scenes, --valid_from_seed,
 --log_dir, --save_dir, --seed, --use_grid_lstm, --loss, --num_samples,
---sample_seed, --head_log_sigma, --collision_radius."""
+--sample_seed, --head_log_sigma, --collision_radius, --fit_head,
+--calibration."""
 import argparse
 
 
@@ -60,6 +61,17 @@ class ArgsParser:
                              'JFDE_K) and the collision rates: two pedestrians collide when they '
                              'come closer than this at any predicted step, in the units of the '
                              "dataset's position columns (0: off)")
+    parser.add_argument('--fit_head', choices=('off', 'train', 'eval'), default='off',
+                        help='--num_samples: before the draws, replace the head by the closed-form '
+                             "maximum-likelihood fit of the residuals on the scenes of the fold's "
+                             'training datasets (train; honours --train_scenes) or of the left-out '
+                             'dataset itself (eval: in-sample, a bound).  eth_hotel is normalised to '
+                             '0..1 and the UCY sets are world coordinates, so a pooled fit mixes '
+                             'the two units')
+    parser.add_argument('--calibration', type=int, default=0,
+                        help='--num_samples: 1 reports the calibration of the head in use on the '
+                             'left-out dataset (NLL per pair, coverage of the 50 / 90 / 95 %% '
+                             'ellipses, ECE, mean(q) / 2); implied by --fit_head train / eval')
     parser.add_argument('--train_scenes', type=int, default=0,
                         help='--mode train: distinct scenes used (0: all of the fold)')
     parser.add_argument('--valid_from_seed', type=int, default=0,

@@ -550,6 +550,45 @@ int g2k_joint_eval_f32(const g2k_dims* d, const float* pred, const float* target
                            (hipStream_t)stream);
 }
 
+static bool head_stats_sizes_ok(const g2k_dims* d, int32_t n_levels) {
+  if (d->S < 0 || d->F < 0 || d->Nmax < 1 || d->Nmax > kMaxN) return false;
+  if (n_levels < 0 || n_levels > 32) return false;
+  return (int64_t)d->S * d->F <= 0x7fffffff;     // scene-frames are indexed in 32 bits
+}
+
+int64_t g2k_head_stats_workspace_bytes(const g2k_dims* d, int32_t n_levels) {
+  if (!d || !head_stats_sizes_ok(d, n_levels)) return -1;
+  return head_stats_ws_bytes(d, n_levels);
+}
+
+int g2k_head_stats_f32(const g2k_dims* d, const float* pred, const float* targets,
+                       const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                       const float* head, const double* r2, int32_t n_levels, double* stats,
+                       int64_t* inside, float* fit, void* workspace, int64_t workspace_bytes,
+                       void* stream) {
+  if (!d) return set_err(G2K_EINVAL, "dims is NULL");
+  if (d->flags & G2K_STEP_PRED_PED_MAJOR)
+    return set_err(G2K_EUNSUPPORTED, "head_stats reads pred_path_band [S, F, 2L, Nmax]");
+  if (!head_stats_sizes_ok(d, n_levels))
+    return set_err(G2K_EINVAL, "S=%d F=%d Nmax=%d n_levels=%d (Nmax 1..256, n_levels 0..32, S F < 2^31)",
+                   d->S, d->F, d->Nmax, n_levels);
+  if (!pred || !targets || !n_active || !stats)
+    return set_err(G2K_EINVAL, "a required buffer pointer is NULL");
+  if (!head && (n_levels > 0 || inside))
+    return set_err(G2K_EINVAL, "head is NULL: n_levels must be 0 and inside NULL");
+  if (n_levels > 0 && !r2) return set_err(G2K_EINVAL, "r2 is NULL with n_levels=%d", n_levels);
+  if (((uintptr_t)targets) & 7) return set_err(G2K_EINVAL, "targets must be 8-byte aligned");
+  if ((((uintptr_t)stats) | ((uintptr_t)inside) | ((uintptr_t)r2)) & 7)
+    return set_err(G2K_EINVAL, "stats, inside and r2 must be 8-byte aligned");
+  const int64_t need = head_stats_ws_bytes(d, n_levels);
+  if (d->S > 0 && need > 0 && (!workspace || workspace_bytes < need || (((uintptr_t)workspace) & 7)))
+    return set_err(G2K_EINVAL, "workspace of %lld bytes needed (got %lld), 8-byte aligned",
+                   (long long)need, (long long)workspace_bytes);
+  if (d->S == 0) return G2K_OK;
+  return head_stats_launch(d, pred, targets, n_active, n_frames, ped_mask, head, r2, n_levels, stats,
+                           inside, fit, workspace, (hipStream_t)stream);
+}
+
 int g2k_update_f32(float* params, float* ms, const float* grad, int64_t n_params, float lr,
                    float decay, float grad_clip, void* stream) {
   if (!params || !grad || n_params < 0 || n_params > (1 << 30))

@@ -517,6 +517,13 @@ int joint_eval_launch(const g2k_dims* d, const float* pred, const float* targets
                       int32_t* per_frame_i, float* sums_f, int64_t* sums_i, int32_t* rows,
                       hipStream_t st);
 
+// g2k_calib.hip
+int64_t head_stats_ws_bytes(const g2k_dims* d, int n_levels);
+int head_stats_launch(const g2k_dims* d, const float* pred, const float* targets,
+                      const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                      const float* head, const double* r2, int n_levels, double* stats,
+                      int64_t* inside, float* fit, void* workspace, hipStream_t st);
+
 // g2k_ops.hip
 int recur_launch(const float* A, float* h, int S, int frames, int D, int H, hipStream_t st);
 int mcr_forward_launch(const g2k_dims* d, const g2k_weights* w, const float* X, const float* Rel,

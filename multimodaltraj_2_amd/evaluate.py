@@ -24,9 +24,19 @@ normalised nor shifted — for the UCY sets (zara01, zara02, ucy_univ) world
 coordinates spanning about -9..5 by -3..3, for eth_hotel image coordinates
 normalised to 0..1.  The head is the checkpoint's (``nll_head/head``, which
 --mode train --loss nll learns) or, for parameters without one, a constant
-exp(--head_log_sigma) per step.  The build's: the reference has no
-probabilistic head, so these figures have no
-reference counterpart.
+exp(--head_log_sigma) per step.  All of these figures depend on how wide that
+head is, so --fit_head train / eval replaces it, before the first draw, by the
+closed-form maximum-likelihood head of the residuals (GaussianHead.fit, one
+g2k_head_stats_f32 launch, csrc/g2k_calib.hip) over the scenes of the fold's
+training datasets (one more fused step over them) or over the left-out scenes
+themselves (in-sample: a bound, not an estimate), and --calibration 1 (implied
+by --fit_head) reports how the head in use fits the left-out scenes: NLL per
+pair, the share of targets inside its 50 / 90 / 95 % ellipses, the expected
+calibration error over the levels 0.1 .. 0.9, 0.95, 0.99 and mean(q) / 2 (1
+when calibrated).  The units caveat above holds for a pooled fit too: eth_hotel
+is normalised, the UCY sets are world coordinates, so a fold that mixes them
+fits one width to both.  The build's: the reference has no probabilistic head
+(SURVEY.md §8(f) row 4), so these figures have no reference counterpart.
 """
 from __future__ import annotations
 
@@ -41,6 +51,16 @@ from .nll import GaussianHead
 FIGURES = ("ade", "fde", "min_ade", "min_fde")
 JOINT_FIGURES = ("jade", "jfde", "ped_pairs", "collision_rate", "collision_rate_pred",
                  "collision_rate_best", "collision_rate_gt")
+CALIB_FIGURES = ("nll", "coverage_50", "coverage_90", "coverage_95", "ece", "q_ratio")
+CALIB_LEVELS = (0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9, 0.95, 0.99)
+
+
+def calib_figures(hs):
+    """CALIB_FIGURES of a HeadStats taken at CALIB_LEVELS."""
+    cov = hs.coverage_all
+    at = {p: float(cov[i]) for i, p in enumerate(hs.levels)}
+    return dict(nll=hs.nll, coverage_50=at[0.5], coverage_90=at[0.9], coverage_95=at[0.95],
+                ece=hs.ece, q_ratio=hs.q_ratio)
 
 
 def left_out_plan(args, nmax):
@@ -58,19 +78,10 @@ def left_out_plan(args, nmax):
     return rd.plan_scenes(n, raw, nmax=nmax)
 
 
-def evaluate_best_of_k(args, params, device, log=print, keep=None):
-    """--num_samples K on --leaveDataset with ``params`` (a G2KParams on
-    ``device``).  Logs and returns {scenes, pairs, K, ade, fde, min_ade,
-    min_fde} (errors per (scene, pedestrian) pair; ade / fde: the mean
-    prediction's), with --collision_radius R > 0 also JOINT_FIGURES from one
-    joint_eval launch and a second log line.  ``keep`` (a dict) receives the
-    plan, the predictions, the head and the kernels' outputs for a caller that
-    checks them."""
+def _fused_step(args, params, plan, device):
+    """One fused step over the plan's scenes (F = 1, stride 0) -> (device
+    tensors, the step's outputs, n_frames = 1 per scene)."""
     from .train import context_G
-    K = int(args.num_samples)
-    if K < 1:
-        raise ValueError("--num_samples K must be >= 1")
-    plan = left_out_plan(args, params.nmax)
     S = plan.S
     t = plan.to_device(device, F=1)
     G = torch.from_numpy(context_G(args.seed, S)).to(device)
@@ -78,6 +89,36 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
     one = torch.ones(S, dtype=torch.int32, device=device)
     out = fs.step_fused(params, t["pos"], t["vislet"], G, t["targets"], t["n_active"], h0,
                         n_frames=one, ped_mask=t["ped_mask"], stride=0, lam=args.lambda_param)
+    return t, out, one
+
+
+def fold_plan(args, nmax):
+    """The RealPlan of the fold's training datasets, as run_train_mode plans
+    them (--train_scenes honoured), at the parameters' Nmax."""
+    raw = rd.load_raw(list(rd.fold_datasets(args.leaveDataset)), args.data_root)
+    return rd.plan_scenes(args.train_scenes or rd.count_scenes(raw, nmax), raw, nmax=nmax)
+
+
+def evaluate_best_of_k(args, params, device, log=print, keep=None):
+    """--num_samples K on --leaveDataset with ``params`` (a G2KParams on
+    ``device``).  Logs and returns {scenes, pairs, K, ade, fde, min_ade,
+    min_fde} (errors per (scene, pedestrian) pair; ade / fde: the mean
+    prediction's), with --collision_radius R > 0 also JOINT_FIGURES from one
+    joint_eval launch and a second log line.  --fit_head train / eval first
+    replaces the head by the closed-form fit (GaussianHead.fit) on the fold's
+    training scenes / on the left-out scenes themselves; --calibration 1
+    (implied by --fit_head) adds CALIB_FIGURES from one stats launch on the
+    left-out scenes with the head in use, and a log line.  ``keep`` (a dict)
+    receives the plan, the predictions, the head and the kernels' outputs for
+    a caller that checks them."""
+    K = int(args.num_samples)
+    if K < 1:
+        raise ValueError("--num_samples K must be >= 1")
+    fit_mode = getattr(args, "fit_head", "off") or "off"
+    calibrate = bool(getattr(args, "calibration", 0)) or fit_mode != "off"
+    plan = left_out_plan(args, params.nmax)
+    S = plan.S
+    t, out, one = _fused_step(args, params, plan, device)
     if params.head is not None:
         gh = GaussianHead(device=device)
         gh.head = params.head.contiguous()
@@ -85,6 +126,18 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
     else:
         gh = GaussianHead(log_sigma=args.head_log_sigma, device=device)
         log(f"best-of-K: no head in the parameters, constant log sigma {args.head_log_sigma}")
+    fitted = None
+    if fit_mode == "train":
+        fplan = fold_plan(args, params.nmax)
+        ft, fout, fone = _fused_step(args, params, fplan, device)
+        fitted = gh.fit(fout.pred, ft["targets"], ft["n_active"], n_frames=fone,
+                        ped_mask=ft["ped_mask"])
+        log(f"best-of-K: head replaced by the closed-form fit on {fplan.S} scenes of the fold's "
+            f"training datasets ({fitted.pairs} pairs)")
+    elif fit_mode == "eval":
+        fitted = gh.fit(out.pred, t["targets"], t["n_active"], n_frames=one, ped_mask=t["ped_mask"])
+        log(f"best-of-K: head replaced by the closed-form fit on the left-out dataset itself "
+            f"({fitted.pairs} pairs): in-sample, a bound and not an estimate")
     bk = gh.best_of_k(out.pred, t["targets"], t["n_active"], K, seed=args.sample_seed, n_frames=one,
                       ped_mask=t["ped_mask"], want_per_ped=False)
     res = dict(scenes=S, pairs=bk.pairs, K=K, ade=bk.ade, fde=bk.fde, min_ade=bk.min_ade,
@@ -103,9 +156,21 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
             f"collision rate: samples {res['collision_rate']:.6g} mean {res['collision_rate_pred']:.6g} "
             f"best joint sample {res['collision_rate_best']:.6g} "
             f"ground truth {res['collision_rate_gt']:.6g}")
+    calib = None
+    if calibrate:
+        calib = gh.stats(out.pred, t["targets"], t["n_active"], CALIB_LEVELS, n_frames=one,
+                         ped_mask=t["ped_mask"])
+        res.update(calib_figures(calib))
+        sig = torch.exp(gh.head[:2]).cpu().numpy()
+        log(f"calibration on dataset {args.leaveDataset}: NLL per pair {res['nll']:.6g}, coverage "
+            f"50% {res['coverage_50']:.4f} 90% {res['coverage_90']:.4f} 95% {res['coverage_95']:.4f}, "
+            f"ECE {res['ece']:.4f}, q_ratio {res['q_ratio']:.6g}, sigma_x / sigma_y step 1 "
+            f"{sig[0, 0]:.6g} / {sig[1, 0]:.6g} step 12 {sig[0, -1]:.6g} / {sig[1, -1]:.6g}")
     if keep is not None:
         keep.update(plan=plan, pred=out.pred, head=gh.head, out=bk, n_frames=np.ones(S, np.int32),
                     joint=joint)
+        if calibrate:
+            keep.update(calib=calib, fitted=fitted)
     return res
 
 

@@ -11,12 +11,16 @@ d nll / d pred; ``sample`` draws one reproducible trajectory per
 (step, pedestrian); ``best_of_k`` evaluates K such draws against the targets
 in one launch (minADE_K / minFDE_K, csrc/g2k_bestk.hip); ``joint_eval``
 scores the same K draws as JOINT samples of a scene-frame (JADE_K / JFDE_K)
-and counts collisions between the pedestrians (csrc/g2k_joint.hip)."""
+and counts collisions between the pedestrians (csrc/g2k_joint.hip);
+``stats`` measures the head's calibration against the targets (coverage of
+its confidence ellipses, per-step NLL) and ``fit`` sets the head to the
+closed-form maximum-likelihood one of the residuals (csrc/g2k_calib.hip)."""
 from __future__ import annotations
 
 import ctypes
 from dataclasses import dataclass
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -119,6 +123,94 @@ class JointEval:
     @property
     def collision_rate_gt(self) -> float:
         return self._rate(3)
+
+
+@dataclass
+class HeadStats:
+    """``GaussianHead.stats``'s outputs (include/g2k_hip.h).  Every property
+    is one host read (float64); a figure whose denominator is 0 is NaN, and
+    those of a head (nll, coverage, ece, q_ratio) are None when the launch had
+    none (``use_head=False``)."""
+    stats: torch.Tensor                 # [12, 8] float64 {pairs, S dx, S dy, S dx2, S dy2, S dxdy, S nll, S q}
+    inside: torch.Tensor | None         # [12, NL] int64: pairs with q_t <= r2[l]
+    fit_head: torch.Tensor              # [3, 12] float32: the closed-form head, written by the device
+    levels: tuple = ()
+    r2: torch.Tensor | None = None      # [NL] float64 on the device
+    has_head: bool = True
+
+    def _s(self):
+        return self.stats.cpu().numpy()
+
+    @property
+    def pairs(self) -> int:
+        return int(self.stats[0, 0].item())
+
+    @property
+    def fit(self) -> torch.Tensor:
+        return self.fit_head
+
+    @property
+    def nll_per_step(self):
+        """[12] mean NLL of a pair at each step."""
+        if not self.has_head:
+            return None
+        s = self._s()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return s[:, 6] / s[:, 0]
+
+    @property
+    def nll(self):
+        """Per pair, summed over the 12 steps."""
+        if not self.has_head:
+            return None
+        s = self._s()
+        return float(s[:, 6].sum() / s[0, 0]) if s[0, 0] > 0 else float("nan")
+
+    @property
+    def coverage(self):
+        """[12, NL]: share of the pairs inside each level's ellipse, per step."""
+        if not self.has_head:
+            return None
+        n = self._s()[:, :1]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return self.inside.cpu().numpy().astype(np.float64) / n
+
+    @property
+    def coverage_all(self):
+        """[NL]: pooled over the 12 steps."""
+        if not self.has_head:
+            return None
+        n = self._s()[:, 0].sum()
+        tot = self.inside.sum(dim=0).cpu().numpy().astype(np.float64)
+        return tot / n if n > 0 else np.full(tot.shape, np.nan)
+
+    @property
+    def ece(self):
+        """mean over the levels of |coverage_all - p|."""
+        if not self.has_head:
+            return None
+        if not self.levels:
+            return float("nan")
+        return float(np.abs(self.coverage_all - np.asarray(self.levels, np.float64)).mean())
+
+    @property
+    def q_ratio(self):
+        """sum q / (2 * 12 * pairs): 1 under a calibrated head."""
+        if not self.has_head:
+            return None
+        s = self._s()
+        return float(s[:, 7].sum() / (2.0 * PRED_LEN * s[0, 0])) if s[0, 0] > 0 else float("nan")
+
+    @property
+    def bias(self):
+        """[12, 2]: mean dx, dy per step."""
+        s = self._s()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return s[:, 1:3] / s[:, :1]
+
+
+MAX_LEVELS = 32
+DEFAULT_LEVELS = (0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9, 0.95, 0.99)
 
 
 class GaussianHead:
@@ -251,6 +343,83 @@ class GaussianHead:
         _lib.check("g2k_joint_eval_f32", rc)
         return JointEval(sums_f=sums_f, sums_i=sums_i, per_frame_f=pf, per_frame_i=pi, k=k,
                          radius=radius)
+
+    def _r2(self, levels, dev):
+        """The levels' radii -2 log1p(-p), float64, on ``dev`` (formed on the
+        host once per set of levels: a repeated call copies nothing)."""
+        cache = self.__dict__.setdefault("_r2_cache", {})
+        key = (levels, str(dev))
+        if key not in cache:
+            cache.clear()
+            cache[key] = (-2.0 * torch.log1p(-torch.tensor(levels, dtype=torch.float64))).to(dev)
+        return cache[key]
+
+    def stats(self, pred, targets, n_active, levels=DEFAULT_LEVELS, *, n_frames=None, ped_mask=None,
+              targets_shared=False, use_head=True, stream=None):
+        """Calibration in one launch (g2k_head_stats_f32): the per-step
+        residual moments over the pairs and their closed-form head (``fit``),
+        and, with ``use_head``, this head's NLL, q = squared Mahalanobis
+        distance and the pairs inside the ``levels``' ellipses (level p: q <=
+        -2 ln(1 - p), the chi^2(2) quantile) -> HeadStats."""
+        levels = tuple(float(p) for p in levels) if use_head else ()
+        if len(levels) > MAX_LEVELS:
+            raise ValueError(f"{len(levels)} levels: {MAX_LEVELS} at most")
+        for p in levels:
+            if not 0.0 < p < 1.0:
+                raise ValueError(f"level {p}: 0 < p < 1")
+        lib = _lib.load()
+        dev = pred.device
+        d = self._dims(pred)
+        S, F, Nmax = d.S, d.F, d.Nmax
+        if targets_shared:
+            d.flags = _lib.STEP_TARGETS_SHARED
+        _check_dev("pred", pred, dev, torch.float32)
+        if use_head:
+            _check_dev("head", self.head, dev, torch.float32)
+        if tuple(n_active.shape) != (S,):
+            raise ValueError("n_active must be [S]")
+        _check_dev("n_active", n_active, dev, torch.int32)
+        tshape = (S, 1 if targets_shared else F, Nmax, PRED_LEN, 2)
+        if tuple(targets.shape) != tshape:
+            raise ValueError(f"targets must be {list(tshape)}")
+        _check_dev("targets", targets, dev, torch.float32)
+        if n_frames is not None:
+            if tuple(n_frames.shape) != (S,):
+                raise ValueError("n_frames must be [S]")
+            _check_dev("n_frames", n_frames, dev, torch.int32)
+        if ped_mask is not None:
+            if tuple(ped_mask.shape) != (S, Nmax):
+                raise ValueError("ped_mask must be [S, Nmax]")
+            _check_dev("ped_mask", ped_mask, dev, torch.uint8)
+        nl = len(levels)
+        r2 = self._r2(levels, dev) if nl else None
+        # S = 0 launches nothing: the outputs are the empty launch's zeros
+        make = torch.zeros if S == 0 else torch.empty
+        stats = make((PRED_LEN, 8), dtype=torch.float64, device=dev)
+        inside = make((PRED_LEN, nl), dtype=torch.int64, device=dev) if use_head else None
+        fit = make((3, PRED_LEN), dtype=torch.float32, device=dev)
+        ws = torch.empty(max(8, int(lib.g2k_head_stats_workspace_bytes(ctypes.byref(d), nl))),
+                         dtype=torch.uint8, device=dev)
+        rc = lib.g2k_head_stats_f32(ctypes.byref(d), _ptr(pred), _ptr(targets), _ptr(n_active),
+                                    _ptr(n_frames), _ptr(ped_mask),
+                                    _ptr(self.head) if use_head else None, _ptr(r2), nl, _ptr(stats),
+                                    _ptr(inside) if nl else None, _ptr(fit), _ptr(ws), ws.numel(),
+                                    _stream(stream))
+        _lib.check("g2k_head_stats_f32", rc)
+        return HeadStats(stats=stats, inside=inside, fit_head=fit, levels=levels, r2=r2,
+                         has_head=bool(use_head))
+
+    def fit(self, pred, targets, n_active, *, n_frames=None, ped_mask=None, targets_shared=False,
+            stream=None):
+        """Set ``self.head`` to the closed-form maximum-likelihood head of the
+        residuals (one stats launch without a head; the device writes the
+        head) -> that launch's HeadStats.  ValueError when there is no pair."""
+        hs = self.stats(pred, targets, n_active, (), n_frames=n_frames, ped_mask=ped_mask,
+                        targets_shared=targets_shared, use_head=False, stream=stream)
+        if hs.pairs == 0:
+            raise ValueError("fit: no (scene, frame, pedestrian) pair to fit the head on")
+        self.head = hs.fit_head
+        return hs
 
     def sample(self, pred, seed=0, stream=None):
         """One draw around pred [S, F, 2L, Nmax] (same layout out)."""
