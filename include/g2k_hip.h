@@ -506,6 +506,68 @@ int g2k_head_stats_f32(const g2k_dims* d, const float* pred, const float* target
                        int64_t* inside, float* fit, void* workspace, int64_t workspace_bytes,
                        void* stream);
 
+/*
+ * The full-covariance trajectory head (added after ABI 11; detect by symbol;
+ * csrc/g2k_fullcov.hip): ONE Gaussian over a pair's whole 24-vector of
+ * residuals, so that a draw is a temporally correlated trajectory (the
+ * per-step head above is its block-diagonal special case).  Inputs and pairs
+ * as g2k_best_of_k_f32.  Coordinate i = 2 t + c (step t, c = 0 for x, 1 for
+ * y): time-major, so a lower-triangular factor is causal in time.
+ *   r[i] = targets[..][t][c] - pred[c 12 + t], in double
+ *   chol [24][24] (f32, row-major) = L, the lower Cholesky factor of the
+ *     residual covariance; its diagonal must be positive (not checked on the
+ *     device); entries j > i are never read
+ *   z[2t], z[2t+1] = the pair of standard normals the sampler forms for
+ *     element e = ((s F + f) 12 + t) Nmax + n and seed (seed + k) mod 2^64
+ *   draw: x[i] = mu[i] + sum_{j <= i} L[i][j] z[j], accumulated as acc = mu[i];
+ *     for j = 0..i: acc = fmaf(L[i][j], z[j], acc); written in band layout,
+ *     out[c 12 + t] = x[2t + c]
+ *   z = L^-1 r (double); q_t = z[2t]^2 + z[2t+1]^2 (step t's innovation given
+ *     the earlier steps: chi^2(2) under a calibrated head), q = sum_t q_t
+ *     (chi^2(24)); nll_t = log 2 pi + log L[2t][2t] + log L[2t+1][2t+1] + q_t / 2,
+ *     the joint NLL is sum_t nll_t
+ * g2k_fullcov_stats_f32, one pass over pred and targets, all in double:
+ *   moments [25][24]: rows 0..23 = M = sum over the pairs of r r^T (both
+ *     triangles written, equal), row 24 = sum r
+ *   stats [12][4] = {pairs, sum nll_t, sum q_t, 0}; columns 1, 2 exactly 0
+ *     when chol is NULL
+ *   inside [13][n_levels] (int64) or NULL: rows 0..11 the pairs with q_t <=
+ *     r2[0][l], row 12 those with q <= r2[1][l]; r2 [2][n_levels] doubles on
+ *     the device
+ *   fit [24][24] (f32) or NULL: the Cholesky factor (computed in double) of
+ *     C = M / pairs with C_ii <- C_ii (1 + 1e-6) + 1e-12, zeros above the
+ *     diagonal; the identity when there is no pair
+ *   Every element of every output is written on every call with S >= 1;
+ *   non-pairs of pred / targets are never read.  chol == NULL requires
+ *   n_levels == 0 and inside == NULL.  n_levels in 0..32, Nmax in 1..256,
+ *   S F < 2^31; moments, stats, inside, r2 and the workspace 8-byte aligned;
+ *   workspace >= g2k_fullcov_stats_workspace_bytes(d, n_levels), which is 0
+ *   when one workgroup covers the launch (else G2K_EINVAL before any launch).
+ *   Fixed summation order, no atomics: repeated calls are bit-identical, and
+ *   the moments' bits do not depend on chol or the levels.
+ * g2k_fullcov_sample_f32: out [S, F, 2L, Nmax] = one draw per (s, f, n), every
+ *   element written; reads d->S, F, Nmax as g2k_gauss_sample_f32.
+ * g2k_fullcov_best_of_k_f32: g2k_best_of_k_f32 with chol in place of head and
+ *   these draws: the same per_ped, best (draw kA, bit-identical to
+ *   g2k_fullcov_sample_f32 at seed + kA, for pairs; pred elsewhere) and out,
+ *   K in 1..4096, no draw in memory, ties to the lowest k.
+ * All three: S = 0 is a no-op; asynchronous, no allocation, capturable.
+ */
+int64_t g2k_fullcov_stats_workspace_bytes(const g2k_dims* d, int32_t n_levels);
+int g2k_fullcov_stats_f32(const g2k_dims* d, const float* pred, const float* targets,
+                          const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                          const float* chol, const double* r2, int32_t n_levels, double* moments,
+                          double* stats, int64_t* inside, float* fit, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+int g2k_fullcov_sample_f32(const g2k_dims* d, const float* pred, const float* chol, uint64_t seed,
+                           float* out, void* stream);
+int64_t g2k_fullcov_best_of_k_workspace_bytes(const g2k_dims* d);
+int g2k_fullcov_best_of_k_f32(const g2k_dims* d, const float* pred, const float* targets,
+                              const int32_t* n_active, const int32_t* n_frames,
+                              const uint8_t* ped_mask, const float* chol, uint64_t seed, int32_t K,
+                              float* per_ped, float* best, float* out, void* workspace,
+                              int64_t workspace_bytes, void* stream);
+
 int64_t g2k_context_conv_workspace_bytes(int32_t Hh, int32_t Ww, int32_t D);
 int g2k_context_conv_f32(const float* img, int32_t Hh, int32_t Ww, int32_t C, const float* filt,
                          int32_t D, float lambda, float* out, float* G, void* workspace,

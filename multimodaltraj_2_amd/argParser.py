@@ -3,7 +3,7 @@ the build's own: --data_root (Q8), --device, --mode,
 --world_size, --n_max, --train_batch, --train_scenes, --valid_from_seed,
 --log_dir, --save_dir, --seed, --use_grid_lstm, --loss, --num_samples,
 --sample_seed, --head_log_sigma, --collision_radius, --fit_head,
---calibration."""
+--calibration, --fullcov_head."""
 import argparse
 
 
@@ -72,6 +72,13 @@ class ArgsParser:
                         help='--num_samples: 1 reports the calibration of the head in use on the '
                              'left-out dataset (NLL per pair, coverage of the 50 / 90 / 95 %% '
                              'ellipses, ECE, mean(q) / 2); implied by --fit_head train / eval')
+    parser.add_argument('--fullcov_head', choices=('off', 'train', 'eval'), default='off',
+                        help='--num_samples: after the per-step figures, also fit the full-covariance '
+                             'trajectory head (one Gaussian over the 24 residuals of a pedestrian, so '
+                             "a draw is a correlated trajectory) on the scenes of the fold's training "
+                             'datasets (train; honours --train_scenes) or of the left-out dataset '
+                             'itself (eval: in-sample, a bound), and report its minADE_K / minFDE_K, '
+                             'joint NLL, coverage and the lag-1 correlation of the residuals')
     parser.add_argument('--train_scenes', type=int, default=0,
                         help='--mode train: distinct scenes used (0: all of the fold)')
     parser.add_argument('--valid_from_seed', type=int, default=0,

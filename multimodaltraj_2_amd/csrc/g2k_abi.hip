@@ -589,6 +589,79 @@ int g2k_head_stats_f32(const g2k_dims* d, const float* pred, const float* target
                            inside, fit, workspace, (hipStream_t)stream);
 }
 
+int64_t g2k_fullcov_stats_workspace_bytes(const g2k_dims* d, int32_t n_levels) {
+  if (!d || !head_stats_sizes_ok(d, n_levels)) return -1;
+  return fullcov_stats_ws_bytes(d, n_levels);
+}
+
+int g2k_fullcov_stats_f32(const g2k_dims* d, const float* pred, const float* targets,
+                          const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                          const float* chol, const double* r2, int32_t n_levels, double* moments,
+                          double* stats, int64_t* inside, float* fit, void* workspace,
+                          int64_t workspace_bytes, void* stream) {
+  if (!d) return set_err(G2K_EINVAL, "dims is NULL");
+  if (d->flags & G2K_STEP_PRED_PED_MAJOR)
+    return set_err(G2K_EUNSUPPORTED, "fullcov_stats reads pred_path_band [S, F, 2L, Nmax]");
+  if (!head_stats_sizes_ok(d, n_levels))
+    return set_err(G2K_EINVAL, "S=%d F=%d Nmax=%d n_levels=%d (Nmax 1..256, n_levels 0..32, S F < 2^31)",
+                   d->S, d->F, d->Nmax, n_levels);
+  if (!pred || !targets || !n_active || !moments || !stats)
+    return set_err(G2K_EINVAL, "a required buffer pointer is NULL");
+  if (!chol && (n_levels > 0 || inside))
+    return set_err(G2K_EINVAL, "chol is NULL: n_levels must be 0 and inside NULL");
+  if (n_levels > 0 && !r2) return set_err(G2K_EINVAL, "r2 is NULL with n_levels=%d", n_levels);
+  if (((uintptr_t)targets) & 7) return set_err(G2K_EINVAL, "targets must be 8-byte aligned");
+  if ((((uintptr_t)moments) | ((uintptr_t)stats) | ((uintptr_t)inside) | ((uintptr_t)r2)) & 7)
+    return set_err(G2K_EINVAL, "moments, stats, inside and r2 must be 8-byte aligned");
+  const int64_t need = fullcov_stats_ws_bytes(d, n_levels);
+  if (d->S > 0 && need > 0 && (!workspace || workspace_bytes < need || (((uintptr_t)workspace) & 7)))
+    return set_err(G2K_EINVAL, "workspace of %lld bytes needed (got %lld), 8-byte aligned",
+                   (long long)need, (long long)workspace_bytes);
+  if (d->S == 0) return G2K_OK;
+  return fullcov_stats_launch(d, pred, targets, n_active, n_frames, ped_mask, chol, r2, n_levels,
+                              moments, stats, inside, fit, workspace, (hipStream_t)stream);
+}
+
+int g2k_fullcov_sample_f32(const g2k_dims* d, const float* pred, const float* chol, uint64_t seed,
+                           float* out, void* stream) {
+  int32_t one = 1;
+  int rc = validate_nll(d, pred, chol, &one);
+  if (rc) return rc;
+  if (!out) return set_err(G2K_EINVAL, "out is NULL");
+  if ((int64_t)d->S * d->F * kL * d->Nmax == 0) return G2K_OK;
+  return fullcov_sample_launch(d, pred, chol, seed, out, (hipStream_t)stream);
+}
+
+int64_t g2k_fullcov_best_of_k_workspace_bytes(const g2k_dims* d) {
+  if (!d || d->S < 0 || d->F < 0) return -1;
+  return fullcov_best_of_k_ws_bytes(d);
+}
+
+int g2k_fullcov_best_of_k_f32(const g2k_dims* d, const float* pred, const float* targets,
+                              const int32_t* n_active, const int32_t* n_frames,
+                              const uint8_t* ped_mask, const float* chol, uint64_t seed, int32_t K,
+                              float* per_ped, float* best, float* out, void* workspace,
+                              int64_t workspace_bytes, void* stream) {
+  if (!d) return set_err(G2K_EINVAL, "dims is NULL");
+  if (d->flags & G2K_STEP_PRED_PED_MAJOR)
+    return set_err(G2K_EUNSUPPORTED, "fullcov_best_of_k reads pred_path_band [S, F, 2L, Nmax]");
+  if (d->S < 0 || d->F < 0 || d->Nmax < 1 || d->Nmax > kMaxN)
+    return set_err(G2K_EINVAL, "S=%d F=%d Nmax=%d", d->S, d->F, d->Nmax);
+  if (K < 1 || K > 4096) return set_err(G2K_EINVAL, "K=%d (1..4096)", K);
+  if (!pred || !targets || !n_active || !chol || !out)
+    return set_err(G2K_EINVAL, "a required buffer pointer is NULL");
+  if (((uintptr_t)targets) & 7) return set_err(G2K_EINVAL, "targets must be 8-byte aligned");
+  if (((uintptr_t)per_ped) & 15) return set_err(G2K_EINVAL, "per_ped must be 16-byte aligned");
+  const int64_t need = fullcov_best_of_k_ws_bytes(d);
+  if (d->S > 0 && (!workspace || workspace_bytes < need))
+    return set_err(G2K_EINVAL, "workspace of %lld bytes needed (got %lld)", (long long)need,
+                   (long long)workspace_bytes);
+  if (d->S == 0) return G2K_OK;
+  return fullcov_best_of_k_launch(d, pred, targets, n_active, n_frames, ped_mask, chol, seed, K,
+                                  per_ped, best, out, static_cast<float*>(workspace),
+                                  (hipStream_t)stream);
+}
+
 int g2k_update_f32(float* params, float* ms, const float* grad, int64_t n_params, float lr,
                    float decay, float grad_clip, void* stream) {
   if (!params || !grad || n_params < 0 || n_params > (1 << 30))

@@ -232,15 +232,22 @@ __device__ __forceinline__ GaussStep gauss_step(const float* __restrict__ head, 
   g.sq = sqrtf(fmaf(-g.rho, g.rho, 1.f));
   return g;
 }
-__device__ __forceinline__ void gauss_draw(uint32_t stream, uint32_t e_lo, const GaussStep& g,
-                                           float mx, float my, float& x, float& y) {
+// the element's pair of standard normals (e1, e2): what every head draws from
+// (the per-step head below, the full-covariance head of g2k_fullcov.hip)
+__device__ __forceinline__ void gauss_normals(uint32_t stream, uint32_t e_lo, float& e1, float& e2) {
   const uint32_t key = stream ^ e_lo;
   const uint32_t h1 = pcg_hash(2u * key + 1u), h2 = pcg_hash(2u * key + 2u);
   const float u1 = ((float)(h1 >> 8) + 0.5f) * (1.0f / 16777216.0f);
   const float u2 = ((float)(h2 >> 8) + 0.5f) * (1.0f / 16777216.0f);
   const float rad = sqrtf(-2.f * logf(u1));
   const float ang = 6.283185307179586f * u2;
-  const float e1 = rad * cosf(ang), e2 = rad * sinf(ang);
+  e1 = rad * cosf(ang);
+  e2 = rad * sinf(ang);
+}
+__device__ __forceinline__ void gauss_draw(uint32_t stream, uint32_t e_lo, const GaussStep& g,
+                                           float mx, float my, float& x, float& y) {
+  float e1, e2;
+  gauss_normals(stream, e_lo, e1, e2);
   x = fmaf(g.sx, e1, mx);
   y = fmaf(g.sy, fmaf(g.rho, e1, g.sq * e2), my);
 }
@@ -523,6 +530,20 @@ int head_stats_launch(const g2k_dims* d, const float* pred, const float* targets
                       const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
                       const float* head, const double* r2, int n_levels, double* stats,
                       int64_t* inside, float* fit, void* workspace, hipStream_t st);
+
+// g2k_fullcov.hip
+int64_t fullcov_stats_ws_bytes(const g2k_dims* d, int n_levels);
+int fullcov_stats_launch(const g2k_dims* d, const float* pred, const float* targets,
+                         const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                         const float* chol, const double* r2, int n_levels, double* moments,
+                         double* stats, int64_t* inside, float* fit, void* workspace, hipStream_t st);
+int fullcov_sample_launch(const g2k_dims* d, const float* pred, const float* chol, uint64_t seed,
+                          float* out, hipStream_t st);
+int64_t fullcov_best_of_k_ws_bytes(const g2k_dims* d);
+int fullcov_best_of_k_launch(const g2k_dims* d, const float* pred, const float* targets,
+                             const int32_t* n_active, const int32_t* n_frames,
+                             const uint8_t* ped_mask, const float* chol, uint64_t seed, int K,
+                             float* per_ped, float* best, float* out, float* rows, hipStream_t st);
 
 // g2k_ops.hip
 int recur_launch(const float* A, float* h, int S, int frames, int D, int H, hipStream_t st);

@@ -33,7 +33,14 @@ themselves (in-sample: a bound, not an estimate), and --calibration 1 (implied
 by --fit_head) reports how the head in use fits the left-out scenes: NLL per
 pair, the share of targets inside its 50 / 90 / 95 % ellipses, the expected
 calibration error over the levels 0.1 .. 0.9, 0.95, 0.99 and mean(q) / 2 (1
-when calibrated).  The units caveat above holds for a pooled fit too: eth_hotel
+when calibrated).  --fullcov_head train / eval then fits, after all of the
+above and on the same predictions, K and seed, the full-covariance trajectory
+head (fullcov.FullCovHead, csrc/g2k_fullcov.hip: one Gaussian over a
+pedestrian's 24 residuals, so that a draw is a temporally correlated
+trajectory and not 12 independent steps) and reports its minADE_K / minFDE_K,
+joint NLL per pair, the share of trajectories inside its 90 % region, sum q /
+24 n and the mean correlation of the x-residuals at adjacent steps: how far
+from independent the steps are.  The units caveat above holds for a pooled fit too: eth_hotel
 is normalised, the UCY sets are world coordinates, so a fold that mixes them
 fits one width to both.  The build's: the reference has no probabilistic head
 (SURVEY.md §8(f) row 4), so these figures have no reference counterpart.
@@ -53,6 +60,8 @@ JOINT_FIGURES = ("jade", "jfde", "ped_pairs", "collision_rate", "collision_rate_
                  "collision_rate_best", "collision_rate_gt")
 CALIB_FIGURES = ("nll", "coverage_50", "coverage_90", "coverage_95", "ece", "q_ratio")
 CALIB_LEVELS = (0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9, 0.95, 0.99)
+FULLCOV_FIGURES = ("fullcov_min_ade", "fullcov_min_fde", "fullcov_nll", "fullcov_coverage_90",
+                   "fullcov_q_ratio", "fullcov_lag1_corr")
 
 
 def calib_figures(hs):
@@ -61,6 +70,15 @@ def calib_figures(hs):
     at = {p: float(cov[i]) for i, p in enumerate(hs.levels)}
     return dict(nll=hs.nll, coverage_50=at[0.5], coverage_90=at[0.9], coverage_95=at[0.95],
                 ece=hs.ece, q_ratio=hs.q_ratio)
+
+
+def fullcov_figures(bk, st):
+    """FULLCOV_FIGURES of a best-of-K result and a FullCovStats taken at
+    CALIB_LEVELS with the same head."""
+    at = {p: float(c) for p, c in zip(st.levels, st.coverage_joint)}
+    return dict(fullcov_min_ade=bk.min_ade, fullcov_min_fde=bk.min_fde, fullcov_nll=st.nll,
+                fullcov_coverage_90=at[0.9], fullcov_q_ratio=st.q_ratio,
+                fullcov_lag1_corr=st.lag1_corr)
 
 
 def left_out_plan(args, nmax):
@@ -108,7 +126,10 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
     replaces the head by the closed-form fit (GaussianHead.fit) on the fold's
     training scenes / on the left-out scenes themselves; --calibration 1
     (implied by --fit_head) adds CALIB_FIGURES from one stats launch on the
-    left-out scenes with the head in use, and a log line.  ``keep`` (a dict)
+    left-out scenes with the head in use, and a log line.  --fullcov_head
+    train / eval then fits a FullCovHead on the same scenes as --fit_head
+    would, runs its stats and best_of_k on the left-out scenes and adds
+    FULLCOV_FIGURES and a log line.  ``keep`` (a dict)
     receives the plan, the predictions, the head and the kernels' outputs for
     a caller that checks them."""
     K = int(args.num_samples)
@@ -166,11 +187,39 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
             f"50% {res['coverage_50']:.4f} 90% {res['coverage_90']:.4f} 95% {res['coverage_95']:.4f}, "
             f"ECE {res['ece']:.4f}, q_ratio {res['q_ratio']:.6g}, sigma_x / sigma_y step 1 "
             f"{sig[0, 0]:.6g} / {sig[1, 0]:.6g} step 12 {sig[0, -1]:.6g} / {sig[1, -1]:.6g}")
+    fc_mode = getattr(args, "fullcov_head", "off") or "off"
+    fc = fc_st = fc_bk = None
+    if fc_mode != "off":
+        from .fullcov import FullCovHead
+        fc = FullCovHead(device=device)
+        if fc_mode == "train":
+            fplan = fold_plan(args, params.nmax)
+            ft, fout, fone = _fused_step(args, params, fplan, device)
+            ffit = fc.fit(fout.pred, ft["targets"], ft["n_active"], n_frames=fone,
+                          ped_mask=ft["ped_mask"])
+            where = f"{fplan.S} scenes of the fold's training datasets ({ffit.pairs} pairs)"
+        else:
+            ffit = fc.fit(out.pred, t["targets"], t["n_active"], n_frames=one, ped_mask=t["ped_mask"])
+            where = (f"the left-out dataset itself ({ffit.pairs} pairs): in-sample, a bound and not "
+                     f"an estimate")
+        fc_st = fc.stats(out.pred, t["targets"], t["n_active"], CALIB_LEVELS, n_frames=one,
+                         ped_mask=t["ped_mask"])
+        fc_bk = fc.best_of_k(out.pred, t["targets"], t["n_active"], K, seed=args.sample_seed,
+                             n_frames=one, ped_mask=t["ped_mask"], want_per_ped=False)
+        res.update(fullcov_figures(fc_bk, fc_st))
+        log(f"full-covariance head on dataset {args.leaveDataset}: closed-form fit on {where}; "
+            f"minADE_{K} {res['fullcov_min_ade']:.6g} minFDE_{K} {res['fullcov_min_fde']:.6g} "
+            f"(per-step head {res['min_ade']:.6g} / {res['min_fde']:.6g}), joint NLL per pair "
+            f"{res['fullcov_nll']:.6g}, coverage 90% {res['fullcov_coverage_90']:.4f}, q_ratio "
+            f"{res['fullcov_q_ratio']:.6g}, lag-1 correlation of the x-residuals "
+            f"{res['fullcov_lag1_corr']:.4f} (left-out scenes)")
     if keep is not None:
         keep.update(plan=plan, pred=out.pred, head=gh.head, out=bk, n_frames=np.ones(S, np.int32),
                     joint=joint)
         if calibrate:
             keep.update(calib=calib, fitted=fitted)
+        if fc is not None:
+            keep.update(fullcov=dict(stats=fc_st, out=fc_bk, fitted=ffit), fullcov_chol=fc.chol)
     return res
 
 
