@@ -144,6 +144,50 @@ int32_t g2k_step_split(const g2k_dims* d);
  * call, so a plan can be sized for its device with or without a GPU present;
  * -1 on invalid dims or cus < 1 (ABI 9). */
 int32_t g2k_step_split_for_cus(const g2k_dims* d, int32_t cus);
+/* The build and the LDS layout a launch of `d` would use (added after ABI 11;
+ * detect by symbol): what the launcher itself works out before it picks one
+ * of the scene kernel's instantiations, from the same functions, reported
+ * instead of launched.  Host arithmetic only, no HIP call: the same answer
+ * with or without a GPU.  `train` != 0: g2k_train_step_f32 (`has_h_in` != 0)
+ * or g2k_step_grad_f32 / g2k_step_grad_update_f32 (`has_h_in` == 0: no
+ * recurrence, the H = 64 build whatever d->H says); `train` == 0:
+ * g2k_step_fused_f32 (`has_h_in` must be != 0).  An automatic split request
+ * is resolved for a device with `cus` compute units, as
+ * g2k_step_split_for_cus does.  out[G2K_GEOM_FIELDS]:
+ *   G2K_GEOM_TPW        threads per recurrence row (H / 64: 1, 2, 4 or 8)
+ *   G2K_GEOM_NP         producer waves (12, 8 or 4)
+ *   G2K_GEOM_FC         frames per LDS chunk (min(F, 32), halved until the
+ *                       scene fits in 160 KB)
+ *   G2K_GEOM_CHUNKS     chunks a scene of F frames takes (ceil(F / fc))
+ *   G2K_GEOM_DWO_SEQ    train: 1 when dWo^T is one copy added in frame order,
+ *                       0 when every worker keeps its own; forward: 0
+ *   G2K_GEOM_OWN0       block ownership size (train, two workgroups per scene,
+ *                       L2 loss), else 0
+ *   G2K_GEOM_SPLIT      workgroups per scene
+ *   G2K_GEOM_VARIANT    G2K_STEP_VARIANT_*: the NLL loss, loop-invariant
+ *                       frames, block ownership, or the general kernel
+ *   G2K_GEOM_LDS_BYTES  dynamic LDS per workgroup
+ *   G2K_GEOM_PED_MAJOR  1: the pedestrian-major pred build
+ * Returns G2K_OK, G2K_EINVAL / G2K_EUNSUPPORTED on bad arguments (dims as the
+ * entry point itself rejects them, out NULL, cus < 1), G2K_ELDS when the
+ * layout does not fit. */
+#define G2K_GEOM_TPW 0
+#define G2K_GEOM_NP 1
+#define G2K_GEOM_FC 2
+#define G2K_GEOM_CHUNKS 3
+#define G2K_GEOM_DWO_SEQ 4
+#define G2K_GEOM_OWN0 5
+#define G2K_GEOM_SPLIT 6
+#define G2K_GEOM_VARIANT 7
+#define G2K_GEOM_LDS_BYTES 8
+#define G2K_GEOM_PED_MAJOR 9
+#define G2K_GEOM_FIELDS 10
+#define G2K_STEP_VARIANT_GENERAL 0
+#define G2K_STEP_VARIANT_NLL 1
+#define G2K_STEP_VARIANT_INV 2
+#define G2K_STEP_VARIANT_BLK 3
+int g2k_step_geometry(const g2k_dims* d, int32_t train, int32_t has_h_in, int32_t cus,
+                      int32_t* out);
 /* Zero-fill `workspace_bytes` bytes of a workspace on `stream` (hipMemsetAsync).
  * (ABI 6 and earlier required it before a split workspace's first use; since
  * ABI 7 every launch zeroes its tickets itself and this is optional.) */

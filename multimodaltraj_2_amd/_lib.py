@@ -34,6 +34,12 @@ STEP_SPLIT_SHIFT = 8           # G2K_STEP_SPLIT(x): workgroups per scene, 0 = au
 STEP_MAX_SPLIT = 4
 
 
+# g2k_step_geometry's out[] (G2K_GEOM_*) and its variant codes (G2K_STEP_VARIANT_*)
+GEOM_FIELDS = ("tpw", "np", "fc", "chunks", "dwo_seq", "own0", "split", "variant", "lds_bytes",
+               "ped_major")
+STEP_VARIANTS = ("general", "nll", "inv", "blk")
+
+
 class G2KWeights(ctypes.Structure):
     _fields_ = [("Wi", c_vp), ("Wii", c_vp), ("Wv", c_vp), ("bv", c_vp), ("Wr", c_vp),
                 ("Wc", c_vp), ("Wo", c_vp), ("head", c_vp)]
@@ -46,6 +52,8 @@ SYMBOLS = {
     "g2k_step_workspace_bytes": (c_i64, [ctypes.POINTER(G2KDims)]),
     "g2k_step_split": (ctypes.c_int32, [ctypes.POINTER(G2KDims)]),
     "g2k_step_split_for_cus": (ctypes.c_int32, [ctypes.POINTER(G2KDims), ctypes.c_int32]),
+    "g2k_step_geometry": (c_int, [ctypes.POINTER(G2KDims), c_i32, c_i32, c_i32,
+                                  ctypes.POINTER(c_i32)]),
     "g2k_workspace_init": (c_int, [c_vp, c_i64, c_vp]),
     "g2k_step_fused_f32": (c_int, [ctypes.POINTER(G2KDims), ctypes.POINTER(G2KWeights),
                                    c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,

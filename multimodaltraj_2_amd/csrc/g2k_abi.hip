@@ -213,6 +213,22 @@ int32_t g2k_step_split_for_cus(const g2k_dims* d, int32_t cus) {
   return scene_split_cus(*d, cus);
 }
 
+int g2k_step_geometry(const g2k_dims* d, int32_t train, int32_t has_h_in, int32_t cus,
+                      int32_t* out) {
+  int rc = validate_common(d, true, false, train ? kTrainFlags : kStepFlags);
+  if (rc) return rc;
+  if (!out) return set_err(G2K_EINVAL, "out is NULL");
+  if (cus < 1) return set_err(G2K_EINVAL, "cus=%d < 1", cus);
+  if (d->stride < 0) return set_err(G2K_EINVAL, "stride=%d < 0", d->stride);
+  if (!train && !has_h_in) return set_err(G2K_EINVAL, "the forward step always has h_in");
+  if (has_h_in && (rc = validate_H(d->H))) return rc;
+  // the split made explicit as a launch does (step_args), for `cus` CUs: no
+  // later scene_split(x) asks the runtime for a device
+  g2k_dims x = *d;
+  if (split_automatic(x)) x.flags |= G2K_STEP_SPLIT(scene_split_cus(x, cus));
+  return scene_geometry(x, train != 0, has_h_in != 0, out);
+}
+
 int64_t g2k_step_workspace_bytes(const g2k_dims* d) {
   if (validate_common(d, true, false, kStepFlags) != G2K_OK) return -1;
   return split_ws_bytes(*d);   // one workgroup per scene: every intermediate stays on chip

@@ -308,7 +308,15 @@ struct RecurH {
       for (int i = 0; i < 4; ++i) store_wt(hs + (4 * q + i) * H + wv * kCols + 16 * t + L, adj[i] * x[t][i]);
   }
 
-  __device__ __forceinline__ void init_max(float* mred, int wv, int q, int L) const {
+  // The loaded h's row maxima over this wave's columns into mred, and the
+  // sums of exp(h) over the same columns into sred (both [NW waves][16 rows]):
+  // with the row maximum M, the whole row's N = sum_j exp(h_j - M) = exp(-M)
+  // sum_j exp(h_j) for init_exp, in the one exchange the maximum needs anyway
+  // (two independent reductions: no round trip between them).
+  // `wide` (wave-uniform): the scene ends after this one frame, see init_exp;
+  // otherwise the sums are neither formed nor read.
+  __device__ __forceinline__ void init_max(float* mred, float* sred, int wv, int q, int L,
+                                           bool wide) const {
     float m[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -318,9 +326,37 @@ struct RecurH {
     }
     const float r = reduce4_rows16<true>(m[0], m[1], m[2], m[3], L);
     if (L < 4) mred[wv * 16 + 4 * q + reduce4_row(L)] = r;
+    if (wide) {
+      float s[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int t = 0; t < TPW; ++t)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) s[i] += __expf(x[t][i]);
+      const float rs = reduce4_rows16<false>(s[0], s[1], s[2], s[3], L);
+      if (L < 4) sred[wv * 16 + 4 * q + reduce4_row(L)] = rs;
+    }
   }
-  // softmax(h) numerators of the loaded h: e_s = 2^-kOff exp(h - max)
-  __device__ __forceinline__ void init_exp(float* red, const float* mred, int wv, int q, int L) {
+  // softmax(h) numerators of the loaded h: e_s = 2^(n - kOff) exp(h - max).
+  // n = 0 for an h as the chain itself produces it (entries in [0, 1]: N ~ H).
+  // An arbitrary h_in may hold rows whose entries lie far below their maximum
+  // (N << H: h_in ~ N(0, 1) has N ~ H / 13 at H = 512); at n = 0 those e_s
+  // fall to 2^-12 and below, where the 2^-25 absolute rounding of the B
+  // operand's lo parts is 2^-13 of them instead of the 2^-18 the split is
+  // sized for (measured: h after ONE frame off by 3e-5 relative for h_in ~
+  // N(0, 1), 7e-4 for N(0, 9); a second frame contracts the error away).
+  // n = floor(log2(H / N)) in 0..9 (an exact scaling, the same in every wave:
+  // each forms it from the same LDS words in the same order) puts the row's
+  // mean e_s back in (2^-8, 2^-7]; the row sums Z_s carry the same factor, so
+  // the A operand b / Z_s compensates with no other change, and 128 As
+  // log2(e) / Z keeps the magnitude the range analysis above assumes.  A row
+  // whose sum of exp(h) leaves the float range (|h| of 70 and more) keeps n = 0.
+  // Only a scene that ENDS after this frame takes the scale (`wide`,
+  // wave-uniform: n_frames == 1): any later frame contracts frame 0's error by
+  // ~1 / H (its numerators are exp of an h' ~ 1 / H), measured 0.03 - 0.3 of
+  // close_h's bound from two frames on with n = 0 — so longer scenes keep the
+  // former arithmetic bit for bit and pay nothing for the statistic.
+  __device__ __forceinline__ void init_exp(float* red, const float* mred, const float* sred, int wv,
+                                           int q, int L, bool wide) {
     float4 m = *reinterpret_cast<const float4*>(mred + 4 * q);
 #pragma unroll
     for (int w = 1; w < NW; ++w) {
@@ -328,13 +364,32 @@ struct RecurH {
       m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
     }
     const float mm[4] = {m.x, m.y, m.z, m.w};
+    static_assert(NW == 4 && (TPW == 1 || TPW == 2 || TPW == 4 || TPW == 8), "H = 64 TPW");
+    float off[4] = {-kOff, -kOff, -kOff, -kOff};
+    if (wide) {
+      float4 sv = *reinterpret_cast<const float4*>(sred + 4 * q);
+#pragma unroll
+      for (int w = 1; w < NW; ++w) {
+        const float4 u = *reinterpret_cast<const float4*>(sred + 16 * w + 4 * q);
+        sv.x += u.x; sv.y += u.y; sv.z += u.z; sv.w += u.w;
+      }
+      const float ss[4] = {sv.x, sv.y, sv.z, sv.w};
+      constexpr float kLog2H = TPW == 1 ? 6.f : TPW == 2 ? 7.f : TPW == 4 ? 8.f : 9.f;   // H = 64 TPW
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        // log2(H / N) = log2 H + M log2(e) - log2(sum_j exp(h_j))
+        const float t = kLog2H + fmaf(mm[i], kLog2e, -__builtin_amdgcn_logf(ss[i]));
+        const bool sane = ss[i] > 1e-30f && ss[i] < 1e30f;
+        off[i] = (sane ? fminf(fmaxf(floorf(t), 0.f), 9.f) : 0.f) - kOff;
+      }
+    }
     float p[4] = {0.f, 0.f, 0.f, 0.f};
     float e[TPW][4];
 #pragma unroll
     for (int t = 0; t < TPW; ++t)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        e[t][i] = __builtin_amdgcn_exp2f(fmaf(x[t][i] - mm[i], kLog2e, -kOff));
+        e[t][i] = __builtin_amdgcn_exp2f(fmaf(x[t][i] - mm[i], kLog2e, off[i]));
         p[i] += e[t][i];
       }
     publish(red, p, wv, q, L);

@@ -744,11 +744,13 @@ __device__ __forceinline__ void scene_recurrence(const StepArgs& a, const SceneL
   if (c.nf > 0)
     scene_stage<NT, NP, PAD>(a, lay, c, 0, c.nf < lay.fc ? c.nf : lay.fc, [&] {
       if (!live) return;
-      rc.init_max(c.sRed + 3 * kRB, c.wv, c.q, c.L);
+      // (partial buffer 1 carries the maxima's companion sums until every wave
+      // has read them: frame 0 publishes into it only once all are at seq 2)
+      rc.init_max(c.sRed + 3 * kRB, c.sRed + kRB, c.wv, c.q, c.L, c.nf == 1);
       asm volatile("" ::: "memory");
       if (c.lane == 0) lds_store_flag(seq + c.wv, 1);
       poll_seq(seq + (c.L & 3), 1);
-      rc.init_exp(c.sRed, c.sRed + 3 * kRB, c.wv, c.q, c.L);
+      rc.init_exp(c.sRed, c.sRed + 3 * kRB, c.sRed + kRB, c.wv, c.q, c.L, c.nf == 1);
       asm volatile("" ::: "memory");
       if (c.lane == 0) lds_store_flag(seq + c.wv, 2);
     });
@@ -1883,7 +1885,14 @@ __device__ __forceinline__ void rec_grad_work(const StepArgs& a, const SceneLayo
                            scene_act_bits(c, scene_mask_word(a, lay, c)),
                            acc, lsum, tg, false, 0, grad_rec_tiles(c.ntact, live));
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (c.lane == 0) atomicAdd(c.sGseq, 1);
+      // only the R waves that had a frame: the producers wait for EXACTLY
+      // NP + R (poll_word compares for equality).  A workgroup without the
+      // chain hands over 1..3 frames when it owns NP + 1 .. NP + 3; with all
+      // four waves counting, the word could pass NP + R while a wave with a
+      // frame was still adding its dU rows (dV, and with it dWi, then missed
+      // them or not from run to run) or skip past it (the producers then
+      // spun to the poll limit)
+      if (c.lane == 0 && c.wv < R) atomicAdd(c.sGseq, 1);
     }
   }
   if (NLL) nll_worker_reduce(c, NP + c.wv);
@@ -2041,18 +2050,33 @@ int scene_producers(const g2k_dims& d, int H, bool grad) {
   return 12;
 }
 
+// The kernel variant of a launch (G2K_STEP_VARIANT_*): the NLL loss (train),
+// loop-invariant frames, block ownership (train, two workgroups per scene),
+// else the general kernel.  launch_kp and scene_geometry both ask here.
+inline int scene_variant(const g2k_dims& d, const SceneLayout& l, bool grad) {
+  if (grad && loss_nll(d)) return G2K_STEP_VARIANT_NLL;
+  if (frames_invariant(d, grad)) return G2K_STEP_VARIANT_INV;   // stride 0, shared targets, one workgroup per scene
+  if (grad && l.own0 > 0) return G2K_STEP_VARIANT_BLK;          // train, two workgroups per scene: block ownership
+  return G2K_STEP_VARIANT_GENERAL;
+}
+
 template <int TPW, int NP, bool GRAD, bool PM>
 void launch_kp(const StepArgs& a, const SceneLayout& l, hipStream_t st) {
   const dim3 grid(a.d.S * l.split), block(64 * (kRecW + NP));
   const size_t lds = (size_t)l.total * 4;
-  if (GRAD && loss_nll(a.d))
-    hipLaunchKernelGGL((g2k_scene_kernel<TPW, NP, GRAD, PM, GRAD, false>), grid, block, lds, st, a, l);
-  else if (frames_invariant(a.d, GRAD))   // stride 0, shared targets, one workgroup per scene
-    hipLaunchKernelGGL((g2k_scene_kernel<TPW, NP, GRAD, PM, false, true>), grid, block, lds, st, a, l);
-  else if (GRAD && l.own0 > 0)           // train, two workgroups per scene: block ownership
-    hipLaunchKernelGGL((g2k_scene_kernel<TPW, NP, GRAD, PM, false, false, GRAD>), grid, block, lds, st, a, l);
-  else
-    hipLaunchKernelGGL((g2k_scene_kernel<TPW, NP, GRAD, PM, false, false>), grid, block, lds, st, a, l);
+  switch (scene_variant(a.d, l, GRAD)) {
+    case G2K_STEP_VARIANT_NLL:
+      hipLaunchKernelGGL((g2k_scene_kernel<TPW, NP, GRAD, PM, GRAD, false>), grid, block, lds, st, a, l);
+      break;
+    case G2K_STEP_VARIANT_INV:
+      hipLaunchKernelGGL((g2k_scene_kernel<TPW, NP, GRAD, PM, false, true>), grid, block, lds, st, a, l);
+      break;
+    case G2K_STEP_VARIANT_BLK:
+      hipLaunchKernelGGL((g2k_scene_kernel<TPW, NP, GRAD, PM, false, false, GRAD>), grid, block, lds, st, a, l);
+      break;
+    default:
+      hipLaunchKernelGGL((g2k_scene_kernel<TPW, NP, GRAD, PM, false, false>), grid, block, lds, st, a, l);
+  }
 }
 
 template <int TPW, int NP, bool GRAD>
@@ -2101,23 +2125,56 @@ int64_t scene_lds_bytes(const g2k_dims* d, bool grad) {
   return (int64_t)scene_layout(d, scene_producers(*d, H, grad), grad).total * 4;
 }
 
+namespace {
+// What a launch of `d` is built from: the recurrence width the build is chosen
+// by (gradient only, no h_in: the recurrence waves idle, the smallest build),
+// the producers, the threads per recurrence row and the LDS layout.
+struct ScenePlan {
+  int H, NP, tpw;
+  SceneLayout l;
+};
+ScenePlan scene_plan(const g2k_dims& d, bool grad, bool has_h_in) {
+  ScenePlan p;
+  p.H = has_h_in ? d.H : 64;
+  p.NP = scene_producers(d, p.H, grad);
+  p.l = scene_layout(&d, p.NP, grad);
+  p.tpw = p.H / 64;
+  return p;
+}
+}  // namespace
+
+int scene_geometry(const g2k_dims& d, bool grad, bool has_h_in, int32_t* out) {
+  const ScenePlan p = scene_plan(d, grad, has_h_in);
+  if ((int64_t)p.l.total * 4 > 160 * 1024)
+    return set_err(G2K_ELDS, "Nmax=%d, stride=%d needs %lld bytes of LDS", d.Nmax, d.stride,
+                   (long long)p.l.total * 4);
+  out[G2K_GEOM_TPW] = p.tpw;
+  out[G2K_GEOM_NP] = p.NP;
+  out[G2K_GEOM_FC] = p.l.fc;
+  out[G2K_GEOM_CHUNKS] = d.F > 0 ? (d.F + p.l.fc - 1) / p.l.fc : 0;
+  out[G2K_GEOM_DWO_SEQ] = grad ? p.l.dwo_seq : 0;
+  out[G2K_GEOM_OWN0] = p.l.own0;
+  out[G2K_GEOM_SPLIT] = p.l.split;
+  out[G2K_GEOM_VARIANT] = scene_variant(d, p.l, grad);
+  out[G2K_GEOM_LDS_BYTES] = p.l.total * 4;
+  out[G2K_GEOM_PED_MAJOR] = (d.flags & G2K_STEP_PRED_PED_MAJOR) ? 1 : 0;
+  return G2K_OK;
+}
+
 int scene_step_launch(const StepArgs& a, hipStream_t st) {
   const bool grad = a.grad_rows != nullptr;
-  // gradient only (no h_in): the recurrence waves idle, the smallest build
-  const int H = a.h_in ? a.d.H : 64;
-  const int NP = scene_producers(a.d, H, grad);
-  const SceneLayout l = scene_layout(&a.d, NP, grad);
+  const ScenePlan p = scene_plan(a.d, grad, a.h_in != nullptr);
+  const SceneLayout& l = p.l;
   if ((int64_t)l.total * 4 > 160 * 1024)
     return set_err(G2K_ELDS, "Nmax=%d, stride=%d needs %lld bytes of LDS", a.d.Nmax, a.d.stride,
                    (long long)l.total * 4);
-  const int tpw = H / 64;
   // split scenes: the scene tickets zeroed on the launch stream first (one
   // 64-byte line per 16 scenes): every launch starts from zero whatever an
   // earlier launch left (an aborted one, a caller's uninitialised workspace)
   if (a.scene_ticket &&
       hipMemsetAsync(a.scene_ticket, 0, (size_t)((a.d.S + 15) / 16) * 64, st) != hipSuccess)
     return set_err(G2K_ELAUNCH, "scene tickets: memset failed");
-  const int rc = grad ? launch_np<true>(a, l, NP, tpw, st) : launch_np<false>(a, l, NP, tpw, st);
+  const int rc = grad ? launch_np<true>(a, l, p.NP, p.tpw, st) : launch_np<false>(a, l, p.NP, p.tpw, st);
   if (rc) return rc;
   return check_launch(grad ? "g2k_scene_kernel (train)" : "g2k_scene_kernel");
 }

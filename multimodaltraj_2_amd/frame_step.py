@@ -185,6 +185,27 @@ def split_for_cus(S, F, split=0, coresident=False, cus=256, *, stride=1, targets
     return x
 
 
+def step_geometry(S, F, H, Nmax, stride=1, *, train=False, has_h_in=True, cus=256,
+                  pred_layout="band", targets_shared=False, loss="l2", split=0,
+                  coresident=False) -> dict:
+    """The scene-kernel build and LDS layout a launch of these dims would use
+    (g2k_step_geometry: host arithmetic, no HIP call — the same answer with or
+    without a GPU): tpw, np, fc, chunks, dwo_seq, own0, split, variant
+    ("general" / "nll" / "inv" / "blk"), lds_bytes, ped_major.  ``train`` with
+    ``has_h_in`` is TrainPlan's launch, without it GradPlan's; an automatic
+    split is resolved for ``cus`` compute units."""
+    lib = _lib.load()
+    W = (max(F, 1) - 1) * stride + OBS_LEN
+    d = _lib.G2KDims(S, F, OBS_LEN, PRED_LEN, HIDDEN_LEN, H, Nmax, W, stride,
+                     step_flags(pred_layout, targets_shared, loss, split, coresident))
+    out = (ctypes.c_int32 * len(_lib.GEOM_FIELDS))()
+    _lib.check("g2k_step_geometry",
+               lib.g2k_step_geometry(ctypes.byref(d), int(train), int(has_h_in), int(cus), out))
+    g = dict(zip(_lib.GEOM_FIELDS, (int(v) for v in out)))
+    g["variant"] = _lib.STEP_VARIANTS[g["variant"]]
+    return g
+
+
 def plan_split(S, F, split, coresident, device, **kw) -> int:
     """The explicit split a plan launches with: an automatic request (0) is
     resolved HERE for the plan's own device and passed to the library as

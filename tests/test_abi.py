@@ -242,6 +242,45 @@ def test_split_sizing_without_a_gpu_is_explicit():
     assert len(sizes) == 3
 
 
+def test_step_geometry_validates_and_agrees_with_the_planning_calls():
+    """g2k_step_geometry (host arithmetic, no HIP call): rejects what the
+    entry points reject, and its split / LDS bytes are g2k_step_split_for_cus's
+    and g2k_step_lds_bytes's for the same dims."""
+    from multimodaltraj_2_amd import frame_step as fs
+    lib = _lib.load()
+    out = (ctypes.c_int32 * len(_lib.GEOM_FIELDS))()
+
+    def call(d, train=0, has_h=1, cus=256, o=out):
+        return lib.g2k_step_geometry(ctypes.byref(d) if d is not None else None, train, has_h, cus, o)
+    assert call(None) == -1
+    assert call(_dims(), o=None) == -1
+    assert call(_dims(), cus=0) == -1 and b"cus" in lib.g2k_last_error()
+    assert call(_dims(stride=-1)) == -1
+    assert call(_dims(T=9)) == -4
+    assert call(_dims(Nmax=300)) == -1
+    assert call(_dims(H=96)) == -4
+    assert call(_dims(H=96), train=1, has_h=0) == 0        # gradient only: H is not read
+    assert call(_dims(), train=0, has_h=0) == -1           # the forward step needs h_in
+    assert call(_dims(flags=_split(5))) == -1
+    assert call(_dims(flags=_lib.STEP_LOSS_NLL)) == -4     # a train-mode flag
+    assert call(_dims(flags=_lib.STEP_LOSS_NLL), train=1) == 0
+    assert call(_dims(flags=_lib.STEP_CORESIDENT), train=1) == -4
+    # train mode keeps the whole scene's window-row gradient [(F-1) stride + 8][16] in LDS
+    assert call(_dims(stride=200, W=19 * 200 + 8), train=1) == -3
+    for S, cus in ((2, 256), (128, 256), (128, 80), (256, 256)):
+        d = _dims(S=S)
+        assert call(d, cus=cus) == 0
+        g = dict(zip(_lib.GEOM_FIELDS, out))
+        assert g["split"] == lib.g2k_step_split_for_cus(ctypes.byref(d), cus)
+        assert (g["tpw"], g["np"], g["fc"], g["chunks"]) == (2, 12, 20, 1)
+        assert g["variant"] == 0 and g["own0"] == 0 and g["dwo_seq"] == 0 and g["ped_major"] == 0
+        assert g["lds_bytes"] == lib.g2k_step_lds_bytes(ctypes.byref(_dims(S=S, flags=_split(g["split"]))))
+    g = fs.step_geometry(128, 20, 128, 32, train=True, split=2)
+    assert (g["variant"], g["np"], g["own0"], g["split"]) == ("blk", 8, 8, 2)
+    g = fs.step_geometry(128, 20, 512, 32, train=True, has_h_in=False, loss="nll", pred_layout="ped")
+    assert (g["variant"], g["tpw"], g["np"], g["ped_major"]) == ("nll", 1, 8, 1)
+
+
 def test_loop_invariant_launches_hold_one_ring_slot():
     """Stride 0 with shared targets and one workgroup per scene
     (g2k_scene.hip frames_invariant): the forward forms one head per chunk,

@@ -63,8 +63,11 @@ g2k_gauss_sample_f32
   2^64 - 1 (both halves of the 64-bit seed, carries between them).
 g2k_update_f32
   P 520 / 1264 / 6676 (Nmax 1, 32, 256 + head: one to seven entries per
-  thread of the 1024), pair count 0 (max(count, 1)) and 7, RMSProp / SGD with
-  and without clipping; a zero gradient with ms = 0.
+  thread of the 1024), 7169 (one entry in the eighth register slot), 8192 (the
+  register path full: kPre * 1024), 8193 (the first size on the strided path:
+  one thread takes a ninth trip) and 20000 (twenty trips, the last partial),
+  pair count 0 (max(count, 1)) and 7, RMSProp / SGD with and without
+  clipping; a zero gradient with ms = 0 at P 1264 and the four sizes above.
 g2k_scene_gather_f32
   a hand-made plan with -1 slots, vis / vis_off given and NULL.
 g2k_encoder_chain_f32
@@ -601,7 +604,7 @@ def test_gauss_sample_domain(lib, S, F, Nmax, seed):
 # ---------------------------------------------------------------------------
 @pytest.mark.parametrize("rms,clip", [(False, 0.0), (True, 10.0), (True, 0.5), (False, 0.5)])
 @pytest.mark.parametrize("count", [0, 7])
-@pytest.mark.parametrize("P", [520, 1264, 6676])
+@pytest.mark.parametrize("P", [520, 1264, 6676, 7169, 8192, 8193, 20000])
 def test_update_domain(lib, P, count, rms, clip):
     rng = np.random.default_rng(9000 + P + count)
     p = f32(rng, P)
@@ -624,15 +627,15 @@ def test_update_domain(lib, P, count, rms, clip):
 @pytest.mark.parametrize("clip", [0.0, 10.0])
 def test_update_zero_gradient_zero_ms(lib, clip):
     rng = np.random.default_rng(9100)
-    P = 1264
-    p = f32(rng, P)
-    ar = Arena("cuda")
-    flat, ms = ar.put(p, "params"), ar.put(np.zeros(P, np.float32), "ms")
-    grad = dev(np.zeros(P + 2, np.float32))
-    ok(lib, lib.g2k_update_f32(ptr(flat), ptr(ms), ptr(grad), P, 5e-3, 0.95, clip, None))
-    ar.check_guards()
-    assert np.array_equal(host(flat).view(np.int32), p.view(np.int32))    # bit-unchanged, finite
-    assert np.all(host(ms) == 0)
+    for P in (1264, 7169, 8192, 8193, 20000):
+        p = f32(rng, P)
+        ar = Arena("cuda")
+        flat, ms = ar.put(p, "params"), ar.put(np.zeros(P, np.float32), "ms")
+        grad = dev(np.zeros(P + 2, np.float32))
+        ok(lib, lib.g2k_update_f32(ptr(flat), ptr(ms), ptr(grad), P, 5e-3, 0.95, clip, None))
+        ar.check_guards()
+        assert np.array_equal(host(flat).view(np.int32), p.view(np.int32)), P    # bit-unchanged, finite
+        assert np.all(host(ms) == 0), P
 
 
 # ---------------------------------------------------------------------------

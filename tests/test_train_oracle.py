@@ -45,6 +45,68 @@ def test_grad_matches_finite_differences(lam):
     assert np.all(g["Wi"][n:] == 0) and np.all(g["Wo"][:, n:] == 0)
 
 
+def _strided_scene(Nmax, n, F, stride, seed):
+    """One scene whose frame f reads window rows f * stride + t (stride 0:
+    every frame the same rows) and has its own targets."""
+    b = make_batch(1, Nmax, 64, F=max((F - 1) * stride, 0) + 1, seed=seed, n_active=[n])
+    tg = b.targets[0][::stride][:F] if stride > 0 else b.targets[0][:1].repeat(F, axis=0).copy()
+    if stride == 0:                       # per-frame targets over the one window
+        tg += 0.01 * np.random.default_rng(seed).standard_normal(tg.shape).astype(tg.dtype)
+    assert tg.shape[0] == F and b.pos.shape[1] >= (F - 1) * stride + 8
+    return b, np.ascontiguousarray(tg)
+
+
+@pytest.mark.parametrize("n", [6, 1])
+@pytest.mark.parametrize("loss", ["l2", "nll"])
+@pytest.mark.parametrize("stride", [0, 2, 9])
+def test_grad_matches_finite_differences_off_stride_1(stride, loss, n):
+    """The same pin at the strides the GPU cells run (tests/step_cells.py):
+    stride 0 (every frame the same window), 2 (overlapping windows) and 9
+    (disjoint windows), L2 and NLL, and one pedestrian (n = 1).  Tolerances as
+    the stride-1 tests': 1e-7 max(1, |loss|) for the L2 loss (quadratic in each
+    parameter: central differences exact up to rounding), 1e-6 max(1, |g|)
+    for the NLL with its smaller steps."""
+    Nmax, F = 8, 3
+    b, tg = _strided_scene(Nmax, n, F, stride, seed=11 + stride)
+    w = _weights(Nmax, seed=2)
+    nll = loss == "nll"
+    if nll:
+        for k in ("Wo", "Wc"):
+            w[k] = 0.05 * w[k]
+    head = 0.3 * np.random.default_rng(8).standard_normal((3, 12)) if nll else None
+    mask = np.ones(Nmax, bool)
+    if n > 1:
+        mask[1] = False
+    args = (b.pos[0], b.vislet[0], b.G[0])
+    kw = dict(n_frames=F, lam=0.05, ped_mask=mask, stride=stride, loss=loss)
+    lval, cnt, g = ref.scene_loss_grad(*args, w, tg, n, head=head, **kw)
+    assert cnt == F * int(mask[:n].sum())
+    rng = np.random.default_rng(3)
+    for k in ref.GRAD_ORDER + (("head",) if nll else ()):
+        for _ in range(4):
+            base = head if k == "head" else w[k]
+            idx = tuple(int(rng.integers(0, s)) for s in base.shape)
+            if k == "Wi":
+                idx = (int(rng.integers(0, n)),) + idx[1:]       # an active row
+            if k == "Wo":
+                idx = idx[:1] + (int(rng.integers(0, n)),)       # an active column
+            if nll:
+                h = (1e-5 if k == "head" else 1e-4) * max(1.0, abs(base[idx]))
+            else:
+                h = 1e-3 * max(1.0, abs(base[idx]))
+
+            def f(delta):
+                hh = None if head is None else head.copy()
+                ww = {kk: v.copy() for kk, v in w.items()}
+                (hh if k == "head" else ww[k])[idx] += delta
+                return ref.scene_loss(*args, ww, tg, n, head=hh, **kw)
+            fd = (f(h) - f(-h)) / (2 * h)
+            bound = 1e-6 * max(1.0, abs(g[k][idx])) if nll else 1e-7 * max(1.0, abs(lval))
+            assert abs(fd - g[k][idx]) <= bound, (k, idx, fd, g[k][idx])
+    assert np.all(g["Wr"] == 0)
+    assert np.all(g["Wi"][n:] == 0) and np.all(g["Wo"][:, n:] == 0)
+
+
 def test_optimizer_update_clip_and_rmsprop():
     rng = np.random.default_rng(2)
     p = rng.standard_normal(50)
