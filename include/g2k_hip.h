@@ -612,6 +612,40 @@ int g2k_fullcov_best_of_k_f32(const g2k_dims* d, const float* pred, const float*
                               float* per_ped, float* best, float* out, void* workspace,
                               int64_t workspace_bytes, void* stream);
 
+/*
+ * Joint best-of-K evaluation of the full-covariance head (added after ABI 11;
+ * detect by symbol; csrc/g2k_fullcov_joint.hip): g2k_joint_eval_f32 with chol
+ * [24][24] in place of head and the correlated draws above, every joint sample
+ * made and used in LDS, none in memory.  Members, P and PP as there.
+ *   joint sample k (k < K) = every member's g2k_fullcov_sample_f32 draw for
+ *     seed (seed + k) mod 2^64 and factor chol, bit for bit (entries j > i of
+ *     chol are never read; a positive diagonal is the caller's contract)
+ *   JADE_k / JFDE_k = mean over members of ADE_k / FDE_k; minJADE, minJFDE
+ *     independently, kJA / kJF the lowest k attaining them
+ *   col(X) = member couples i < j with min_t |X_i(t) - X_j(t)|^2 < radius^2
+ *     over the 12 predicted steps (f32: fmaf(dx, dx, dy * dy) < radius * radius;
+ *     radius 0 counts nothing)
+ *   per_frame_f [S, F, 4] or NULL: {minJADE, minJFDE, kJA, kJF}
+ *   per_frame_i [S, F, 6] or NULL: {P, PP, col(mean), col(targets),
+ *     sum_k col(draw k), col(draw kJA)}; columns 0..3 do not depend on the
+ *     head: they are g2k_joint_eval_f32's
+ *   sums_f [S, 4] = {sum_f P minJADE, sum_f P minJFDE, K, 0}, fixed order
+ *   sums_i [S, 6] (int64, 8-byte aligned) = sum_f of the per_frame_i columns
+ * Every element is written; scene-frames with P = 0 or f >= n_frames[s] get
+ * zeros.  K in 1..4096, Nmax in 1..256, radius finite and >= 0, workspace
+ * (4-byte aligned) >= g2k_fullcov_joint_eval_workspace_bytes(d) (else
+ * G2K_EINVAL before any launch); S = 0 is a no-op.  Asynchronous, no
+ * allocation, capturable; no atomics: repeated calls are bit-identical and the
+ * results do not depend on how the draws are dealt to the workgroups.
+ */
+int64_t g2k_fullcov_joint_eval_workspace_bytes(const g2k_dims* d);
+int g2k_fullcov_joint_eval_f32(const g2k_dims* d, const float* pred, const float* targets,
+                               const int32_t* n_active, const int32_t* n_frames,
+                               const uint8_t* ped_mask, const float* chol, uint64_t seed,
+                               int32_t K, float radius, float* per_frame_f, int32_t* per_frame_i,
+                               float* sums_f, int64_t* sums_i, void* workspace,
+                               int64_t workspace_bytes, void* stream);
+
 int64_t g2k_context_conv_workspace_bytes(int32_t Hh, int32_t Ww, int32_t D);
 int g2k_context_conv_f32(const float* img, int32_t Hh, int32_t Ww, int32_t C, const float* filt,
                          int32_t D, float lambda, float* out, float* G, void* workspace,

@@ -678,6 +678,39 @@ int g2k_fullcov_best_of_k_f32(const g2k_dims* d, const float* pred, const float*
                                   (hipStream_t)stream);
 }
 
+int64_t g2k_fullcov_joint_eval_workspace_bytes(const g2k_dims* d) {
+  if (!d || d->S < 0 || d->F < 0) return -1;
+  return fullcov_joint_eval_ws_bytes(d);
+}
+
+int g2k_fullcov_joint_eval_f32(const g2k_dims* d, const float* pred, const float* targets,
+                               const int32_t* n_active, const int32_t* n_frames,
+                               const uint8_t* ped_mask, const float* chol, uint64_t seed,
+                               int32_t K, float radius, float* per_frame_f, int32_t* per_frame_i,
+                               float* sums_f, int64_t* sums_i, void* workspace,
+                               int64_t workspace_bytes, void* stream) {
+  if (!d) return set_err(G2K_EINVAL, "dims is NULL");
+  if (d->flags & G2K_STEP_PRED_PED_MAJOR)
+    return set_err(G2K_EUNSUPPORTED, "fullcov_joint_eval reads pred_path_band [S, F, 2L, Nmax]");
+  if (d->S < 0 || d->F < 0 || d->Nmax < 1 || d->Nmax > kMaxN)
+    return set_err(G2K_EINVAL, "S=%d F=%d Nmax=%d", d->S, d->F, d->Nmax);
+  if (K < 1 || K > 4096) return set_err(G2K_EINVAL, "K=%d (1..4096)", K);
+  if (!(radius >= 0.f) || radius > 3.402823466e38f)
+    return set_err(G2K_EINVAL, "radius=%g (finite, >= 0)", (double)radius);
+  if (!pred || !targets || !n_active || !chol || !sums_f || !sums_i)
+    return set_err(G2K_EINVAL, "a required buffer pointer is NULL");
+  if (((uintptr_t)targets) & 7) return set_err(G2K_EINVAL, "targets must be 8-byte aligned");
+  if (((uintptr_t)sums_i) & 7) return set_err(G2K_EINVAL, "sums_i must be 8-byte aligned");
+  const int64_t need = fullcov_joint_eval_ws_bytes(d);
+  if (d->S > 0 && (!workspace || workspace_bytes < need || (((uintptr_t)workspace) & 3)))
+    return set_err(G2K_EINVAL, "workspace of %lld bytes needed (got %lld), 4-byte aligned",
+                   (long long)need, (long long)workspace_bytes);
+  if (d->S == 0) return G2K_OK;
+  return fullcov_joint_eval_launch(d, pred, targets, n_active, n_frames, ped_mask, chol, seed, K,
+                                   radius, per_frame_f, per_frame_i, sums_f, sums_i,
+                                   static_cast<int32_t*>(workspace), (hipStream_t)stream);
+}
+
 int g2k_update_f32(float* params, float* ms, const float* grad, int64_t n_params, float lr,
                    float decay, float grad_clip, void* stream) {
   if (!params || !grad || n_params < 0 || n_params > (1 << 30))

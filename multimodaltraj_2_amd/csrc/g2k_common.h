@@ -526,6 +526,16 @@ int joint_eval_launch(const g2k_dims* d, const float* pred, const float* targets
                       const float* head, uint64_t seed, int K, float radius, float* per_frame_f,
                       int32_t* per_frame_i, float* sums_f, int64_t* sums_i, int32_t* rows,
                       hipStream_t st);
+int joint_rows_launch(const g2k_dims* d, const int32_t* rows, int KD, int K, float* per_frame_f,
+                      int32_t* per_frame_i, float* sums_f, int64_t* sums_i, hipStream_t st);
+
+// g2k_fullcov_joint.hip
+int64_t fullcov_joint_eval_ws_bytes(const g2k_dims* d);
+int fullcov_joint_eval_launch(const g2k_dims* d, const float* pred, const float* targets,
+                              const int32_t* n_active, const int32_t* n_frames,
+                              const uint8_t* ped_mask, const float* chol, uint64_t seed, int K,
+                              float radius, float* per_frame_f, int32_t* per_frame_i, float* sums_f,
+                              int64_t* sums_i, int32_t* rows, hipStream_t st);
 
 // g2k_calib.hip
 int64_t head_stats_ws_bytes(const g2k_dims* d, int n_levels);

@@ -40,7 +40,11 @@ pedestrian's 24 residuals, so that a draw is a temporally correlated
 trajectory and not 12 independent steps) and reports its minADE_K / minFDE_K,
 joint NLL per pair, the share of trajectories inside its 90 % region, sum q /
 24 n and the mean correlation of the x-residuals at adjacent steps: how far
-from independent the steps are.  The units caveat above holds for a pooled fit too: eth_hotel
+from independent the steps are.  With --collision_radius R > 0 as well, one
+g2k_fullcov_joint_eval_f32 launch (csrc/g2k_fullcov_joint.hip) follows: the
+same K correlated draws taken as joint samples (FULLCOV_JOINT_FIGURES: JADE_K,
+JFDE_K, the collision rate of the samples and of each scene's best joint
+sample), logged next to the per-step head's.  The units caveat above holds for a pooled fit too: eth_hotel
 is normalised, the UCY sets are world coordinates, so a fold that mixes them
 fits one width to both.  The build's: the reference has no probabilistic head
 (SURVEY.md §8(f) row 4), so these figures have no reference counterpart.
@@ -62,6 +66,8 @@ CALIB_FIGURES = ("nll", "coverage_50", "coverage_90", "coverage_95", "ece", "q_r
 CALIB_LEVELS = (0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9, 0.95, 0.99)
 FULLCOV_FIGURES = ("fullcov_min_ade", "fullcov_min_fde", "fullcov_nll", "fullcov_coverage_90",
                    "fullcov_q_ratio", "fullcov_lag1_corr")
+FULLCOV_JOINT_FIGURES = ("fullcov_jade", "fullcov_jfde", "fullcov_collision_rate",
+                         "fullcov_collision_rate_best")
 
 
 def calib_figures(hs):
@@ -79,6 +85,14 @@ def fullcov_figures(bk, st):
     return dict(fullcov_min_ade=bk.min_ade, fullcov_min_fde=bk.min_fde, fullcov_nll=st.nll,
                 fullcov_coverage_90=at[0.9], fullcov_q_ratio=st.q_ratio,
                 fullcov_lag1_corr=st.lag1_corr)
+
+
+def fullcov_joint_figures(je):
+    """FULLCOV_JOINT_FIGURES of a FullCovHead.joint_eval result (the mean's and
+    the ground truth's collision rates do not depend on the head: they are in
+    JOINT_FIGURES)."""
+    return dict(fullcov_jade=je.jade, fullcov_jfde=je.jfde, fullcov_collision_rate=je.collision_rate,
+                fullcov_collision_rate_best=je.collision_rate_best)
 
 
 def left_out_plan(args, nmax):
@@ -129,7 +143,9 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
     left-out scenes with the head in use, and a log line.  --fullcov_head
     train / eval then fits a FullCovHead on the same scenes as --fit_head
     would, runs its stats and best_of_k on the left-out scenes and adds
-    FULLCOV_FIGURES and a log line.  ``keep`` (a dict)
+    FULLCOV_FIGURES and a log line, and with --collision_radius R > 0 also
+    FULLCOV_JOINT_FIGURES from one FullCovHead.joint_eval launch and one more
+    log line (``keep["fullcov"]["joint"]``).  ``keep`` (a dict)
     receives the plan, the predictions, the head and the kernels' outputs for
     a caller that checks them."""
     K = int(args.num_samples)
@@ -188,7 +204,7 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
             f"ECE {res['ece']:.4f}, q_ratio {res['q_ratio']:.6g}, sigma_x / sigma_y step 1 "
             f"{sig[0, 0]:.6g} / {sig[1, 0]:.6g} step 12 {sig[0, -1]:.6g} / {sig[1, -1]:.6g}")
     fc_mode = getattr(args, "fullcov_head", "off") or "off"
-    fc = fc_st = fc_bk = None
+    fc = fc_st = fc_bk = fc_joint = None
     if fc_mode != "off":
         from .fullcov import FullCovHead
         fc = FullCovHead(device=device)
@@ -213,6 +229,17 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
             f"{res['fullcov_nll']:.6g}, coverage 90% {res['fullcov_coverage_90']:.4f}, q_ratio "
             f"{res['fullcov_q_ratio']:.6g}, lag-1 correlation of the x-residuals "
             f"{res['fullcov_lag1_corr']:.4f} (left-out scenes)")
+        if radius > 0:
+            fc_joint = fc.joint_eval(out.pred, t["targets"], t["n_active"], K, radius,
+                                     seed=args.sample_seed, n_frames=one, ped_mask=t["ped_mask"],
+                                     want_per_frame=keep is not None)
+            res.update(fullcov_joint_figures(fc_joint))
+            log(f"full-covariance joint best-of-K on dataset {args.leaveDataset}: radius {radius:g}, "
+                f"K {K}, JADE_{K} {res['fullcov_jade']:.6g} JFDE_{K} {res['fullcov_jfde']:.6g} "
+                f"(per-step head {res['jade']:.6g} / {res['jfde']:.6g}), collision rate: samples "
+                f"{res['fullcov_collision_rate']:.6g} (per-step head {res['collision_rate']:.6g}) "
+                f"best joint sample {res['fullcov_collision_rate_best']:.6g} (per-step head "
+                f"{res['collision_rate_best']:.6g})")
     if keep is not None:
         keep.update(plan=plan, pred=out.pred, head=gh.head, out=bk, n_frames=np.ones(S, np.int32),
                     joint=joint)
@@ -220,6 +247,8 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
             keep.update(calib=calib, fitted=fitted)
         if fc is not None:
             keep.update(fullcov=dict(stats=fc_st, out=fc_bk, fitted=ffit), fullcov_chol=fc.chol)
+            if fc_joint is not None:
+                keep["fullcov"]["joint"] = fc_joint
     return res
 
 

@@ -10,8 +10,10 @@ parity is unpinned (tests/fullcov_ref.py is the float64 checker).
 ``stats`` measures a head against the targets in one launch (the residuals'
 second moments, the joint NLL, the innovations q_t and their coverage),
 ``fit`` sets the head to the closed-form maximum-likelihood one, ``sample``
-draws one reproducible trajectory per (scene, frame, pedestrian) and
-``best_of_k`` evaluates K such draws against the targets in one launch."""
+draws one reproducible trajectory per (scene, frame, pedestrian),
+``best_of_k`` evaluates K such draws against the targets in one launch and
+``joint_eval`` takes them as joint samples of a scene-frame (JADE_K / JFDE_K
+and the collision counts, csrc/g2k_fullcov_joint.hip), also in one launch."""
 from __future__ import annotations
 
 import ctypes
@@ -23,7 +25,7 @@ import torch
 
 from . import _lib
 from .frame_step import OBS_LEN, PRED_LEN, _check_dev, _ptr, _stream
-from .nll import DEFAULT_LEVELS, MAX_LEVELS, BestOfK
+from .nll import DEFAULT_LEVELS, MAX_LEVELS, BestOfK, JointEval
 
 DIM = 2 * PRED_LEN
 
@@ -320,3 +322,41 @@ class FullCovHead:
                                            ws.numel(), _stream(stream))
         _lib.check("g2k_fullcov_best_of_k_f32", rc)
         return BestOfK(sums=sums, per_ped=per_ped, best=best)
+
+    def joint_eval(self, pred, targets, n_active, k, radius, seed=0, *, n_frames=None, ped_mask=None,
+                   targets_shared=False, want_per_frame=True, stream=None):
+        """Joint best-of-K evaluation in one launch (g2k_fullcov_joint_eval_f32):
+        draw i < k of EVERY member of a scene-frame is ``sample(pred, seed +
+        i)``; per scene-frame the smallest mean ADE / FDE over the members
+        (JADE_K / JFDE_K) and the couples that come closer than ``radius`` at
+        any of the 12 predicted steps, in the draws, the mean prediction and the
+        targets -> nll.JointEval (GaussianHead.joint_eval with this head's
+        correlated draws)."""
+        lib = _lib.load()
+        dev = pred.device
+        d = self._dims(pred)
+        self._check_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
+        self._check_chol(dev)
+        k = int(k)
+        if not 1 <= k <= 4096:
+            raise ValueError(f"k = {k}: 1..4096")
+        radius = float(radius)
+        if not (math.isfinite(radius) and radius >= 0.0):
+            raise ValueError(f"radius = {radius}: finite and >= 0")
+        if dev.type != "cuda":
+            raise ValueError(f"pred: on {dev}, expected a GPU tensor")
+        S, F = d.S, d.F
+        sums_f = torch.empty((S, 4), dtype=torch.float32, device=dev)
+        sums_i = torch.empty((S, 6), dtype=torch.int64, device=dev)
+        pf = torch.empty((S, F, 4), dtype=torch.float32, device=dev) if want_per_frame else None
+        pi = torch.empty((S, F, 6), dtype=torch.int32, device=dev) if want_per_frame else None
+        ws = torch.empty(max(1, int(lib.g2k_fullcov_joint_eval_workspace_bytes(ctypes.byref(d)))),
+                         dtype=torch.uint8, device=dev)
+        rc = lib.g2k_fullcov_joint_eval_f32(ctypes.byref(d), _ptr(pred), _ptr(targets), _ptr(n_active),
+                                            _ptr(n_frames), _ptr(ped_mask), _ptr(self.chol),
+                                            ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), k,
+                                            ctypes.c_float(radius), _ptr(pf), _ptr(pi), _ptr(sums_f),
+                                            _ptr(sums_i), _ptr(ws), ws.numel(), _stream(stream))
+        _lib.check("g2k_fullcov_joint_eval_f32", rc)
+        return JointEval(sums_f=sums_f, sums_i=sums_i, per_frame_f=pf, per_frame_i=pi, k=k,
+                         radius=radius)
