@@ -1,8 +1,10 @@
 """GPU: --use_grid_lstm's encoder chain as ONE workgroup walking the frames
 (g2k_encoder_chain_f32, ABI 8; multimodaltraj_2_amd/encoder_step.py) against
 the same three bodies as three launches per frame issued from a Python loop
-(the round-4 form): bit-identical pred, attn, cost and hidden state, and the
-time per frame of each.  Parity of the chain against the oracle is
+(the round-4 form): bit-identical pred, attn, cost and hidden state at every
+H and cell shape the launcher builds, and the time per frame of each.  Parity
+of the chain against the oracle is tests/test_encoder_chain_builds_gpu.py
+(every build) and
 tests/test_train_legs_gpu.py::test_training_leg_with_grid_lstm_encoder."""
 import json
 import time
@@ -40,22 +42,24 @@ def python_loop(params, cell, pos, vislet, G, n_active, n_frames, h, F, lam=fs.L
     return pred, attn, cost, h
 
 
-def setup(gpu, S, F, H=128, Nmax=32, seed=5):
+def setup(gpu, S, F, H=128, Nmax=32, seed=5, num_layers=2, grid_size=4):
     b = make_batch(S, Nmax, H, F=F, seed=seed)
     t = b.to_device(gpu)
     n_frames = torch.tensor([F - (s % 3) for s in range(S)], dtype=torch.int32, device=gpu)
     G = torch.from_numpy(np.random.default_rng(seed).standard_normal((S, 16, 8)).astype(np.float32)).to(gpu)
     params = fs.init_params(Nmax, seed=1, device=gpu)
-    cell = neighborhood_vis_loc_encoder(hidden_size=H, hidden_len=16, num_layers=2, grid_size=4,
+    cell = neighborhood_vis_loc_encoder(hidden_size=H, hidden_len=16, num_layers=num_layers, grid_size=grid_size,
                                         embedding_size=64, device=gpu, seed=3).rnn
     h0 = torch.from_numpy(np.random.default_rng(seed + 1).standard_normal((1, 16, H)).astype(np.float32)).to(gpu)
     return t, n_frames, G, params, cell, h0
 
 
+@pytest.mark.parametrize("u,fsz", [(1, 2), (2, 4), (4, 8)])
 @pytest.mark.parametrize("H", [64, 128, 256, 512])
-def test_chain_entry_bit_identical_to_python_loop(gpu, H):
+def test_chain_entry_bit_identical_to_python_loop(gpu, H, u, fsz):
     S, F = 5, 7
-    t, n_frames, G, params, cell, h0 = setup(gpu, S, F, H=H)
+    t, n_frames, G, params, cell, h0 = setup(gpu, S, F, H=H, num_layers=u, grid_size=fsz)
+    assert (cell.num_units, cell.feature_size) == (u, fsz)
     n_frames[2] = 0                                   # a batch without frames: skipped
     h_c, h_p = h0.clone(), h0.clone()
     out, _ = EncoderChain(params, cell).run(t["pos"], t["vislet"], G, t["targets"], t["n_active"],

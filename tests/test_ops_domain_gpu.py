@@ -71,7 +71,8 @@ g2k_update_f32
 g2k_scene_gather_f32
   a hand-made plan with -1 slots, vis / vis_off given and NULL.
 g2k_encoder_chain_f32
-  n_frames [2, 0]: a batch without frames is skipped, its outputs untouched.
+  n_frames [2, 0]: a batch without frames is skipped, its outputs untouched
+  (every build and the kernel's other edges: test_encoder_chain_builds_gpu.py).
 g2k_step_fused_f32 / g2k_train_step_f32
   n_active 1 / 16 / 17 / 30 at Nmax 30: one tile, a full tile, a second
   (clipped) tile; n_frames 5 / 0 / 3 / 5; band and ped-major; split 1 and 2.
