@@ -614,7 +614,7 @@ int g2k_fullcov_best_of_k_f32(const g2k_dims* d, const float* pred, const float*
 
 /*
  * Joint best-of-K evaluation of the full-covariance head (added after ABI 11;
- * detect by symbol; csrc/g2k_fullcov_joint.hip): g2k_joint_eval_f32 with chol
+ * detect by symbol; csrc/g2k_joint.hip): g2k_joint_eval_f32 with chol
  * [24][24] in place of head and the correlated draws above, every joint sample
  * made and used in LDS, none in memory.  Members, P and PP as there.
  *   joint sample k (k < K) = every member's g2k_fullcov_sample_f32 draw for

@@ -506,37 +506,87 @@ int g2k_gauss_sample_f32(const g2k_dims* d, const float* pred, const float* head
   return gauss_sample_launch(d, pred, head, seed, out, (hipStream_t)stream);
 }
 
-int64_t g2k_best_of_k_workspace_bytes(const g2k_dims* d) {
-  if (!d || d->S < 0 || d->F < 0) return -1;
-  return best_of_k_ws_bytes(d);
+// The argument checks of the four sampled evaluations (marginal and joint
+// best-of-K of either head); `name` is the entry point's in the message.  The
+// marginal pair: `out` is out, `out2` the optional per_ped (16-byte aligned).
+// The joint pair: `out` is sums_f, `out2` the required sums_i (8-byte
+// aligned), and radius and the workspace's alignment are checked too.  T and
+// L are not looked at.  G2K_OK with S > 0: launch.
+static int validate_sampled(const char* name, bool joint, const g2k_dims* d, const void* pred,
+                            const void* targets, const void* n_active, const void* head, int32_t K,
+                            float radius, const void* out, const void* out2, const void* workspace,
+                            int64_t workspace_bytes) {
+  if (!d) return set_err(G2K_EINVAL, "dims is NULL");
+  if (d->flags & G2K_STEP_PRED_PED_MAJOR)
+    return set_err(G2K_EUNSUPPORTED, "%s reads pred_path_band [S, F, 2L, Nmax]", name);
+  if (d->S < 0 || d->F < 0 || d->Nmax < 1 || d->Nmax > kMaxN)
+    return set_err(G2K_EINVAL, "S=%d F=%d Nmax=%d", d->S, d->F, d->Nmax);
+  if (K < 1 || K > 4096) return set_err(G2K_EINVAL, "K=%d (1..4096)", K);
+  if (joint && (!(radius >= 0.f) || radius > 3.402823466e38f))
+    return set_err(G2K_EINVAL, "radius=%g (finite, >= 0)", (double)radius);
+  if (!pred || !targets || !n_active || !head || !out || (joint && !out2))
+    return set_err(G2K_EINVAL, "a required buffer pointer is NULL");
+  if (((uintptr_t)targets) & 7) return set_err(G2K_EINVAL, "targets must be 8-byte aligned");
+  if (joint && (((uintptr_t)out2) & 7)) return set_err(G2K_EINVAL, "sums_i must be 8-byte aligned");
+  if (!joint && (((uintptr_t)out2) & 15)) return set_err(G2K_EINVAL, "per_ped must be 16-byte aligned");
+  const int64_t need = joint ? joint_eval_ws_bytes(d) : best_of_k_ws_bytes(d);
+  if (d->S > 0 && (!workspace || workspace_bytes < need || (joint && (((uintptr_t)workspace) & 3))))
+    return set_err(G2K_EINVAL, "workspace of %lld bytes needed (got %lld)%s", (long long)need,
+                   (long long)workspace_bytes, joint ? ", 4-byte aligned" : "");
+  return G2K_OK;
 }
+
+static int best_of_k(bool fullcov, const g2k_dims* d, const float* pred, const float* targets,
+                     const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                     const float* head, uint64_t seed, int32_t K, float* per_ped, float* best,
+                     float* out, void* workspace, int64_t workspace_bytes, void* stream) {
+  const int rc = validate_sampled(fullcov ? "fullcov_best_of_k" : "best_of_k", false, d, pred, targets,
+                                  n_active, head, K, 0.f, out, per_ped, workspace, workspace_bytes);
+  if (rc || d->S == 0) return rc;
+  return best_of_k_launch(fullcov, d, pred, targets, n_active, n_frames, ped_mask, head, seed, K,
+                          per_ped, best, out, static_cast<float*>(workspace), (hipStream_t)stream);
+}
+
+static int joint_eval(bool fullcov, const g2k_dims* d, const float* pred, const float* targets,
+                      const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                      const float* head, uint64_t seed, int32_t K, float radius, float* per_frame_f,
+                      int32_t* per_frame_i, float* sums_f, int64_t* sums_i, void* workspace,
+                      int64_t workspace_bytes, void* stream) {
+  const int rc = validate_sampled(fullcov ? "fullcov_joint_eval" : "joint_eval", true, d, pred, targets,
+                                  n_active, head, K, radius, sums_f, sums_i, workspace,
+                                  workspace_bytes);
+  if (rc || d->S == 0) return rc;
+  return joint_eval_launch(fullcov, d, pred, targets, n_active, n_frames, ped_mask, head, seed, K,
+                           radius, per_frame_f, per_frame_i, sums_f, sums_i,
+                           static_cast<int32_t*>(workspace), (hipStream_t)stream);
+}
+
+// the two heads share both evaluations' geometry, so their workspaces too
+static int64_t sampled_ws_bytes(const g2k_dims* d, bool joint) {
+  if (!d || d->S < 0 || d->F < 0) return -1;
+  return joint ? joint_eval_ws_bytes(d) : best_of_k_ws_bytes(d);
+}
+
+int64_t g2k_best_of_k_workspace_bytes(const g2k_dims* d) { return sampled_ws_bytes(d, false); }
+int64_t g2k_fullcov_best_of_k_workspace_bytes(const g2k_dims* d) { return sampled_ws_bytes(d, false); }
+int64_t g2k_joint_eval_workspace_bytes(const g2k_dims* d) { return sampled_ws_bytes(d, true); }
+int64_t g2k_fullcov_joint_eval_workspace_bytes(const g2k_dims* d) { return sampled_ws_bytes(d, true); }
 
 int g2k_best_of_k_f32(const g2k_dims* d, const float* pred, const float* targets,
                       const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
                       const float* head, uint64_t seed, int32_t K, float* per_ped, float* best,
                       float* out, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (!d) return set_err(G2K_EINVAL, "dims is NULL");
-  if (d->flags & G2K_STEP_PRED_PED_MAJOR)
-    return set_err(G2K_EUNSUPPORTED, "best_of_k reads pred_path_band [S, F, 2L, Nmax]");
-  if (d->S < 0 || d->F < 0 || d->Nmax < 1 || d->Nmax > kMaxN)
-    return set_err(G2K_EINVAL, "S=%d F=%d Nmax=%d", d->S, d->F, d->Nmax);
-  if (K < 1 || K > 4096) return set_err(G2K_EINVAL, "K=%d (1..4096)", K);
-  if (!pred || !targets || !n_active || !head || !out)
-    return set_err(G2K_EINVAL, "a required buffer pointer is NULL");
-  if (((uintptr_t)targets) & 7) return set_err(G2K_EINVAL, "targets must be 8-byte aligned");
-  if (((uintptr_t)per_ped) & 15) return set_err(G2K_EINVAL, "per_ped must be 16-byte aligned");
-  const int64_t need = best_of_k_ws_bytes(d);
-  if (d->S > 0 && (!workspace || workspace_bytes < need))
-    return set_err(G2K_EINVAL, "workspace of %lld bytes needed (got %lld)", (long long)need,
-                   (long long)workspace_bytes);
-  if (d->S == 0) return G2K_OK;
-  return best_of_k_launch(d, pred, targets, n_active, n_frames, ped_mask, head, seed, K, per_ped,
-                          best, out, static_cast<float*>(workspace), (hipStream_t)stream);
+  return best_of_k(false, d, pred, targets, n_active, n_frames, ped_mask, head, seed, K, per_ped, best,
+                   out, workspace, workspace_bytes, stream);
 }
 
-int64_t g2k_joint_eval_workspace_bytes(const g2k_dims* d) {
-  if (!d || d->S < 0 || d->F < 0) return -1;
-  return joint_eval_ws_bytes(d);
+int g2k_fullcov_best_of_k_f32(const g2k_dims* d, const float* pred, const float* targets,
+                              const int32_t* n_active, const int32_t* n_frames,
+                              const uint8_t* ped_mask, const float* chol, uint64_t seed, int32_t K,
+                              float* per_ped, float* best, float* out, void* workspace,
+                              int64_t workspace_bytes, void* stream) {
+  return best_of_k(true, d, pred, targets, n_active, n_frames, ped_mask, chol, seed, K, per_ped, best,
+                   out, workspace, workspace_bytes, stream);
 }
 
 int g2k_joint_eval_f32(const g2k_dims* d, const float* pred, const float* targets,
@@ -544,32 +594,56 @@ int g2k_joint_eval_f32(const g2k_dims* d, const float* pred, const float* target
                        const float* head, uint64_t seed, int32_t K, float radius, float* per_frame_f,
                        int32_t* per_frame_i, float* sums_f, int64_t* sums_i, void* workspace,
                        int64_t workspace_bytes, void* stream) {
-  if (!d) return set_err(G2K_EINVAL, "dims is NULL");
-  if (d->flags & G2K_STEP_PRED_PED_MAJOR)
-    return set_err(G2K_EUNSUPPORTED, "joint_eval reads pred_path_band [S, F, 2L, Nmax]");
-  if (d->S < 0 || d->F < 0 || d->Nmax < 1 || d->Nmax > kMaxN)
-    return set_err(G2K_EINVAL, "S=%d F=%d Nmax=%d", d->S, d->F, d->Nmax);
-  if (K < 1 || K > 4096) return set_err(G2K_EINVAL, "K=%d (1..4096)", K);
-  if (!(radius >= 0.f) || radius > 3.402823466e38f)
-    return set_err(G2K_EINVAL, "radius=%g (finite, >= 0)", (double)radius);
-  if (!pred || !targets || !n_active || !head || !sums_f || !sums_i)
-    return set_err(G2K_EINVAL, "a required buffer pointer is NULL");
-  if (((uintptr_t)targets) & 7) return set_err(G2K_EINVAL, "targets must be 8-byte aligned");
-  if (((uintptr_t)sums_i) & 7) return set_err(G2K_EINVAL, "sums_i must be 8-byte aligned");
-  const int64_t need = joint_eval_ws_bytes(d);
-  if (d->S > 0 && (!workspace || workspace_bytes < need || (((uintptr_t)workspace) & 3)))
-    return set_err(G2K_EINVAL, "workspace of %lld bytes needed (got %lld), 4-byte aligned",
-                   (long long)need, (long long)workspace_bytes);
-  if (d->S == 0) return G2K_OK;
-  return joint_eval_launch(d, pred, targets, n_active, n_frames, ped_mask, head, seed, K, radius,
-                           per_frame_f, per_frame_i, sums_f, sums_i, static_cast<int32_t*>(workspace),
-                           (hipStream_t)stream);
+  return joint_eval(false, d, pred, targets, n_active, n_frames, ped_mask, head, seed, K, radius,
+                    per_frame_f, per_frame_i, sums_f, sums_i, workspace, workspace_bytes, stream);
+}
+
+int g2k_fullcov_joint_eval_f32(const g2k_dims* d, const float* pred, const float* targets,
+                               const int32_t* n_active, const int32_t* n_frames,
+                               const uint8_t* ped_mask, const float* chol, uint64_t seed,
+                               int32_t K, float radius, float* per_frame_f, int32_t* per_frame_i,
+                               float* sums_f, int64_t* sums_i, void* workspace,
+                               int64_t workspace_bytes, void* stream) {
+  return joint_eval(true, d, pred, targets, n_active, n_frames, ped_mask, chol, seed, K, radius,
+                    per_frame_f, per_frame_i, sums_f, sums_i, workspace, workspace_bytes, stream);
 }
 
 static bool head_stats_sizes_ok(const g2k_dims* d, int32_t n_levels) {
   if (d->S < 0 || d->F < 0 || d->Nmax < 1 || d->Nmax > kMaxN) return false;
   if (n_levels < 0 || n_levels > 32) return false;
   return (int64_t)d->S * d->F <= 0x7fffffff;     // scene-frames are indexed in 32 bits
+}
+
+// The argument checks of the two calibration entry points: the per-step
+// head's (`name` head_stats, `head_name` head, moments NULL, need =
+// head_stats_ws_bytes) and the full-covariance head's (fullcov_stats, chol,
+// its required moments, fullcov_stats_ws_bytes).  T and L are not looked at.
+static int validate_stats(const char* name, const char* head_name, bool has_moments,
+                          const g2k_dims* d, const void* pred, const void* targets,
+                          const void* n_active, const void* head, const void* r2, int32_t n_levels,
+                          const void* moments, const void* stats, const void* inside,
+                          int64_t (*ws_bytes)(const g2k_dims*, int), const void* workspace,
+                          int64_t workspace_bytes) {
+  if (!d) return set_err(G2K_EINVAL, "dims is NULL");
+  if (d->flags & G2K_STEP_PRED_PED_MAJOR)
+    return set_err(G2K_EUNSUPPORTED, "%s reads pred_path_band [S, F, 2L, Nmax]", name);
+  if (!head_stats_sizes_ok(d, n_levels))
+    return set_err(G2K_EINVAL, "S=%d F=%d Nmax=%d n_levels=%d (Nmax 1..256, n_levels 0..32, S F < 2^31)",
+                   d->S, d->F, d->Nmax, n_levels);
+  if (!pred || !targets || !n_active || (has_moments && !moments) || !stats)
+    return set_err(G2K_EINVAL, "a required buffer pointer is NULL");
+  if (!head && (n_levels > 0 || inside))
+    return set_err(G2K_EINVAL, "%s is NULL: n_levels must be 0 and inside NULL", head_name);
+  if (n_levels > 0 && !r2) return set_err(G2K_EINVAL, "r2 is NULL with n_levels=%d", n_levels);
+  if (((uintptr_t)targets) & 7) return set_err(G2K_EINVAL, "targets must be 8-byte aligned");
+  if ((((uintptr_t)moments) | ((uintptr_t)stats) | ((uintptr_t)inside) | ((uintptr_t)r2)) & 7)
+    return set_err(G2K_EINVAL, "%sstats, inside and r2 must be 8-byte aligned",
+                   has_moments ? "moments, " : "");
+  const int64_t need = ws_bytes(d, n_levels);
+  if (d->S > 0 && need > 0 && (!workspace || workspace_bytes < need || (((uintptr_t)workspace) & 7)))
+    return set_err(G2K_EINVAL, "workspace of %lld bytes needed (got %lld), 8-byte aligned",
+                   (long long)need, (long long)workspace_bytes);
+  return G2K_OK;
 }
 
 int64_t g2k_head_stats_workspace_bytes(const g2k_dims* d, int32_t n_levels) {
@@ -582,25 +656,10 @@ int g2k_head_stats_f32(const g2k_dims* d, const float* pred, const float* target
                        const float* head, const double* r2, int32_t n_levels, double* stats,
                        int64_t* inside, float* fit, void* workspace, int64_t workspace_bytes,
                        void* stream) {
-  if (!d) return set_err(G2K_EINVAL, "dims is NULL");
-  if (d->flags & G2K_STEP_PRED_PED_MAJOR)
-    return set_err(G2K_EUNSUPPORTED, "head_stats reads pred_path_band [S, F, 2L, Nmax]");
-  if (!head_stats_sizes_ok(d, n_levels))
-    return set_err(G2K_EINVAL, "S=%d F=%d Nmax=%d n_levels=%d (Nmax 1..256, n_levels 0..32, S F < 2^31)",
-                   d->S, d->F, d->Nmax, n_levels);
-  if (!pred || !targets || !n_active || !stats)
-    return set_err(G2K_EINVAL, "a required buffer pointer is NULL");
-  if (!head && (n_levels > 0 || inside))
-    return set_err(G2K_EINVAL, "head is NULL: n_levels must be 0 and inside NULL");
-  if (n_levels > 0 && !r2) return set_err(G2K_EINVAL, "r2 is NULL with n_levels=%d", n_levels);
-  if (((uintptr_t)targets) & 7) return set_err(G2K_EINVAL, "targets must be 8-byte aligned");
-  if ((((uintptr_t)stats) | ((uintptr_t)inside) | ((uintptr_t)r2)) & 7)
-    return set_err(G2K_EINVAL, "stats, inside and r2 must be 8-byte aligned");
-  const int64_t need = head_stats_ws_bytes(d, n_levels);
-  if (d->S > 0 && need > 0 && (!workspace || workspace_bytes < need || (((uintptr_t)workspace) & 7)))
-    return set_err(G2K_EINVAL, "workspace of %lld bytes needed (got %lld), 8-byte aligned",
-                   (long long)need, (long long)workspace_bytes);
-  if (d->S == 0) return G2K_OK;
+  const int rc = validate_stats("head_stats", "head", false, d, pred, targets, n_active, head, r2,
+                                n_levels, nullptr, stats, inside, head_stats_ws_bytes, workspace,
+                                workspace_bytes);
+  if (rc || d->S == 0) return rc;
   return head_stats_launch(d, pred, targets, n_active, n_frames, ped_mask, head, r2, n_levels, stats,
                            inside, fit, workspace, (hipStream_t)stream);
 }
@@ -615,25 +674,10 @@ int g2k_fullcov_stats_f32(const g2k_dims* d, const float* pred, const float* tar
                           const float* chol, const double* r2, int32_t n_levels, double* moments,
                           double* stats, int64_t* inside, float* fit, void* workspace,
                           int64_t workspace_bytes, void* stream) {
-  if (!d) return set_err(G2K_EINVAL, "dims is NULL");
-  if (d->flags & G2K_STEP_PRED_PED_MAJOR)
-    return set_err(G2K_EUNSUPPORTED, "fullcov_stats reads pred_path_band [S, F, 2L, Nmax]");
-  if (!head_stats_sizes_ok(d, n_levels))
-    return set_err(G2K_EINVAL, "S=%d F=%d Nmax=%d n_levels=%d (Nmax 1..256, n_levels 0..32, S F < 2^31)",
-                   d->S, d->F, d->Nmax, n_levels);
-  if (!pred || !targets || !n_active || !moments || !stats)
-    return set_err(G2K_EINVAL, "a required buffer pointer is NULL");
-  if (!chol && (n_levels > 0 || inside))
-    return set_err(G2K_EINVAL, "chol is NULL: n_levels must be 0 and inside NULL");
-  if (n_levels > 0 && !r2) return set_err(G2K_EINVAL, "r2 is NULL with n_levels=%d", n_levels);
-  if (((uintptr_t)targets) & 7) return set_err(G2K_EINVAL, "targets must be 8-byte aligned");
-  if ((((uintptr_t)moments) | ((uintptr_t)stats) | ((uintptr_t)inside) | ((uintptr_t)r2)) & 7)
-    return set_err(G2K_EINVAL, "moments, stats, inside and r2 must be 8-byte aligned");
-  const int64_t need = fullcov_stats_ws_bytes(d, n_levels);
-  if (d->S > 0 && need > 0 && (!workspace || workspace_bytes < need || (((uintptr_t)workspace) & 7)))
-    return set_err(G2K_EINVAL, "workspace of %lld bytes needed (got %lld), 8-byte aligned",
-                   (long long)need, (long long)workspace_bytes);
-  if (d->S == 0) return G2K_OK;
+  const int rc = validate_stats("fullcov_stats", "chol", true, d, pred, targets, n_active, chol, r2,
+                                n_levels, moments, stats, inside, fullcov_stats_ws_bytes, workspace,
+                                workspace_bytes);
+  if (rc || d->S == 0) return rc;
   return fullcov_stats_launch(d, pred, targets, n_active, n_frames, ped_mask, chol, r2, n_levels,
                               moments, stats, inside, fit, workspace, (hipStream_t)stream);
 }
@@ -646,69 +690,6 @@ int g2k_fullcov_sample_f32(const g2k_dims* d, const float* pred, const float* ch
   if (!out) return set_err(G2K_EINVAL, "out is NULL");
   if ((int64_t)d->S * d->F * kL * d->Nmax == 0) return G2K_OK;
   return fullcov_sample_launch(d, pred, chol, seed, out, (hipStream_t)stream);
-}
-
-int64_t g2k_fullcov_best_of_k_workspace_bytes(const g2k_dims* d) {
-  if (!d || d->S < 0 || d->F < 0) return -1;
-  return fullcov_best_of_k_ws_bytes(d);
-}
-
-int g2k_fullcov_best_of_k_f32(const g2k_dims* d, const float* pred, const float* targets,
-                              const int32_t* n_active, const int32_t* n_frames,
-                              const uint8_t* ped_mask, const float* chol, uint64_t seed, int32_t K,
-                              float* per_ped, float* best, float* out, void* workspace,
-                              int64_t workspace_bytes, void* stream) {
-  if (!d) return set_err(G2K_EINVAL, "dims is NULL");
-  if (d->flags & G2K_STEP_PRED_PED_MAJOR)
-    return set_err(G2K_EUNSUPPORTED, "fullcov_best_of_k reads pred_path_band [S, F, 2L, Nmax]");
-  if (d->S < 0 || d->F < 0 || d->Nmax < 1 || d->Nmax > kMaxN)
-    return set_err(G2K_EINVAL, "S=%d F=%d Nmax=%d", d->S, d->F, d->Nmax);
-  if (K < 1 || K > 4096) return set_err(G2K_EINVAL, "K=%d (1..4096)", K);
-  if (!pred || !targets || !n_active || !chol || !out)
-    return set_err(G2K_EINVAL, "a required buffer pointer is NULL");
-  if (((uintptr_t)targets) & 7) return set_err(G2K_EINVAL, "targets must be 8-byte aligned");
-  if (((uintptr_t)per_ped) & 15) return set_err(G2K_EINVAL, "per_ped must be 16-byte aligned");
-  const int64_t need = fullcov_best_of_k_ws_bytes(d);
-  if (d->S > 0 && (!workspace || workspace_bytes < need))
-    return set_err(G2K_EINVAL, "workspace of %lld bytes needed (got %lld)", (long long)need,
-                   (long long)workspace_bytes);
-  if (d->S == 0) return G2K_OK;
-  return fullcov_best_of_k_launch(d, pred, targets, n_active, n_frames, ped_mask, chol, seed, K,
-                                  per_ped, best, out, static_cast<float*>(workspace),
-                                  (hipStream_t)stream);
-}
-
-int64_t g2k_fullcov_joint_eval_workspace_bytes(const g2k_dims* d) {
-  if (!d || d->S < 0 || d->F < 0) return -1;
-  return fullcov_joint_eval_ws_bytes(d);
-}
-
-int g2k_fullcov_joint_eval_f32(const g2k_dims* d, const float* pred, const float* targets,
-                               const int32_t* n_active, const int32_t* n_frames,
-                               const uint8_t* ped_mask, const float* chol, uint64_t seed,
-                               int32_t K, float radius, float* per_frame_f, int32_t* per_frame_i,
-                               float* sums_f, int64_t* sums_i, void* workspace,
-                               int64_t workspace_bytes, void* stream) {
-  if (!d) return set_err(G2K_EINVAL, "dims is NULL");
-  if (d->flags & G2K_STEP_PRED_PED_MAJOR)
-    return set_err(G2K_EUNSUPPORTED, "fullcov_joint_eval reads pred_path_band [S, F, 2L, Nmax]");
-  if (d->S < 0 || d->F < 0 || d->Nmax < 1 || d->Nmax > kMaxN)
-    return set_err(G2K_EINVAL, "S=%d F=%d Nmax=%d", d->S, d->F, d->Nmax);
-  if (K < 1 || K > 4096) return set_err(G2K_EINVAL, "K=%d (1..4096)", K);
-  if (!(radius >= 0.f) || radius > 3.402823466e38f)
-    return set_err(G2K_EINVAL, "radius=%g (finite, >= 0)", (double)radius);
-  if (!pred || !targets || !n_active || !chol || !sums_f || !sums_i)
-    return set_err(G2K_EINVAL, "a required buffer pointer is NULL");
-  if (((uintptr_t)targets) & 7) return set_err(G2K_EINVAL, "targets must be 8-byte aligned");
-  if (((uintptr_t)sums_i) & 7) return set_err(G2K_EINVAL, "sums_i must be 8-byte aligned");
-  const int64_t need = fullcov_joint_eval_ws_bytes(d);
-  if (d->S > 0 && (!workspace || workspace_bytes < need || (((uintptr_t)workspace) & 3)))
-    return set_err(G2K_EINVAL, "workspace of %lld bytes needed (got %lld), 4-byte aligned",
-                   (long long)need, (long long)workspace_bytes);
-  if (d->S == 0) return G2K_OK;
-  return fullcov_joint_eval_launch(d, pred, targets, n_active, n_frames, ped_mask, chol, seed, K,
-                                   radius, per_frame_f, per_frame_i, sums_f, sums_i,
-                                   static_cast<int32_t*>(workspace), (hipStream_t)stream);
 }
 
 int g2k_update_f32(float* params, float* ms, const float* grad, int64_t n_params, float lr,

@@ -1,17 +1,21 @@
 // g2k_bestk.hip — fused best-of-K sampling evaluation (minADE_K / minFDE_K)
-// of the bivariate-Gaussian head (g2k_nll.hip).  The build's: the reference
-// has no probabilistic head, so PARITY UNPINNED; tests/bestk_ref.py restates
-// the definition over oracle/g2k_ref.py gauss_sample.
+// of a probabilistic head: ONE kernel, best_of_k_kernel<Head>, instantiated
+// for the per-step bivariate-Gaussian head (g2k_best_of_k_f32) and for the
+// full-covariance trajectory head (g2k_fullcov_best_of_k_f32); the heads are
+// the policies of g2k_head_draw.h.  The build's: the reference has no
+// probabilistic head, so PARITY UNPINNED; tests/bestk_ref.py restates the
+// definition over oracle/g2k_ref.py gauss_sample, tests/fullcov_ref.py the
+// full-covariance draw.
 //
 // Definition.  Inputs as g2k_nll_f32: pred [S, F, 2L, Nmax] (band layout),
 // targets [S, F, Nmax, L, 2] ([S, 1, Nmax, L, 2] with G2K_STEP_TARGETS_SHARED),
-// n_active [S], n_frames [S] or NULL, ped_mask [S, Nmax] or NULL, head [3, 12],
-// seed (uint64), K in [1, 4096].  A pair is (s, f, n) with f < n_frames[s],
-// n < n_active[s], ped_mask[s][n] != 0 (the pairs of the a9 errors and of both
-// train losses).
-//   draw k (k = 0..K-1) = what g2k_gauss_sample_f32 writes for seed
-//     (seed + k) mod 2^64: element e = ((s F + f) 12 + t) Nmax + n through
-//     gauss_draw (g2k_common.h), the sampler's own code
+// n_active [S], n_frames [S] or NULL, ped_mask [S, Nmax] or NULL, the head's
+// parameters (head [3, 12] or chol [24, 24]), seed (uint64), K in [1, 4096].
+// A pair is (s, f, n) with f < n_frames[s], n < n_active[s], ped_mask[s][n] !=
+// 0 (the pairs of the a9 errors and of both train losses).
+//   draw k (k = 0..K-1) = what the head's sampler (g2k_gauss_sample_f32,
+//     g2k_fullcov_sample_f32) writes for seed (seed + k) mod 2^64: element
+//     e = ((s F + f) 12 + t) Nmax + n through the sampler's own code
 //   ADE_k(s,f,n) = 1/12 sum_t ||draw_k(t) - target(t)||_2
 //   FDE_k        = ||draw_k(11) - target(11)||_2
 //   minADE = min_k ADE_k, minFDE = min_k FDE_k (independently); kA / kF the
@@ -28,9 +32,10 @@
 // Geometry.  One workgroup of 256 threads per (scene, chunk of FC frames).  A
 // work item is (pair, slice): the K draws of a pair are dealt round-robin to
 // KS = 2^j adjacent lanes (k = slice, slice + KS, ...); each lane holds the
-// pair's 12 means and 12 targets in registers, draws in registers and keeps
-// its running minima; the KS lanes' minima are combined by a butterfly on
-// (value, index), lexicographic, so the lowest k wins a tie whatever KS is.
+// pair's 24 means and 24 target coordinates in registers (time-major, [2t +
+// c]), draws in registers and keeps its running minima; the KS lanes' minima
+// are combined by a butterfly on (value, index), lexicographic, so the lowest k
+// wins a tie whatever KS is.
 // KS and FC come from the shapes alone (bestk_geom): KS grows until the launch
 // has ~2 * 256 CUs * 1024 items or K is used up, FC fills the 256 threads —
 // S 256 x F 20 x Nmax 32 runs KS 4, FC 2 (2560 workgroups), real-data
@@ -41,6 +46,7 @@
 // g2k_bestk_rows_kernel adds a scene's C rows in chunk order (no atomics);
 // C == 1 writes out directly.
 #include "g2k_common.h"
+#include "g2k_head_draw.h"
 
 namespace g2k {
 namespace {
@@ -65,17 +71,14 @@ BestkGeom bestk_geom(const g2k_dims& d, int K) {
   return g;
 }
 
-__device__ __forceinline__ float sgpr(float v) {
-  return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(v)));
-}
-
-__global__ void __launch_bounds__(kBkThreads) g2k_best_of_k_kernel(
+template <class Head>
+__global__ void __launch_bounds__(kBkThreads) best_of_k_kernel(
     const float* __restrict__ pred, const float* __restrict__ targets,
     const int32_t* __restrict__ n_active, const int32_t* __restrict__ n_frames,
-    const uint8_t* __restrict__ ped_mask, const float* __restrict__ head, int F, int Nmax, int FC,
-    int C, int ks_log2, int K, uint32_t seed_lo, uint32_t seed_hi, int shared_targets,
+    const uint8_t* __restrict__ ped_mask, const float* __restrict__ head_params, int F, int Nmax,
+    int FC, int C, int ks_log2, int K, uint32_t seed_lo, uint32_t seed_hi, int shared_targets,
     float* __restrict__ per_ped, float* __restrict__ best, float* __restrict__ rows) {
-  __shared__ float4 hs[kL];
+  __shared__ typename Head::Lds hlds;
   __shared__ float part[kBkThreads / 64][5];
   const int tid = threadIdx.x;
   const int s = blockIdx.x / C, c = blockIdx.x - s * C;
@@ -86,10 +89,7 @@ __global__ void __launch_bounds__(kBkThreads) g2k_best_of_k_kernel(
   const int nfc = clampi(nf - f0, 0, fcn);                 // ... of them below n_frames
   const uint8_t* mask = ped_mask ? ped_mask + (size_t)s * Nmax : nullptr;
 
-  if (tid < kL) {
-    const GaussStep g = gauss_step(head, tid);
-    hs[tid] = make_float4(g.sx, g.sy, g.rho, g.sq);
-  }
+  Head::stage(head_params, hlds, tid, kBkThreads);
   // non-pairs: zeros in per_ped, pred in best
   if (per_ped || best) {
     for (int idx = tid; idx < fcn * Nmax; idx += kBkThreads) {
@@ -106,12 +106,8 @@ __global__ void __launch_bounds__(kBkThreads) g2k_best_of_k_kernel(
     }
   }
   __syncthreads();
-  GaussStep gs[kL];                                        // wave-uniform: scalar registers
-#pragma unroll
-  for (int t = 0; t < kL; ++t) {
-    const float4 v = hs[t];
-    gs[t].sx = sgpr(v.x); gs[t].sy = sgpr(v.y); gs[t].rho = sgpr(v.z); gs[t].sq = sgpr(v.w);
-  }
+  Head head;
+  head.bind(hlds);
 
   const int KS = 1 << ks_log2;
   const int j = tid & (KS - 1);                            // this lane's slice of the draws
@@ -126,29 +122,17 @@ __global__ void __launch_bounds__(kBkThreads) g2k_best_of_k_kernel(
     const size_t pb = sf * kL2 * Nmax + n;
     const int64_t e0 = (int64_t)(sf * kL) * Nmax + n;      // element of step 0
     float mu[kL2], tg[kL2];
+    load_mu_tg(on, pred, targets, sf, shared_targets ? (size_t)s : sf, n, Nmax, mu, tg);
     float pa = 0.f, pf = 0.f;                              // ADE / FDE of the mean prediction
     if (on) {
-      const size_t tf = shared_targets ? (size_t)s : sf;
-      const float2* t2 = reinterpret_cast<const float2*>(targets) + (tf * Nmax + n) * kL;
 #pragma unroll
       for (int t = 0; t < kL; ++t) {
-        mu[t] = pred[pb + (size_t)t * Nmax];
-        mu[kL + t] = pred[pb + (size_t)(kL + t) * Nmax];
-        const float2 v = t2[t];
-        tg[2 * t] = v.x; tg[2 * t + 1] = v.y;
-      }
-#pragma unroll
-      for (int t = 0; t < kL; ++t) {
-        const float dx = mu[t] - tg[2 * t], dy = mu[kL + t] - tg[2 * t + 1];
+        const float dx = mu[2 * t] - tg[2 * t], dy = mu[2 * t + 1] - tg[2 * t + 1];
         pf = sqrtf(fmaf(dx, dx, dy * dy));
         pa += pf;
       }
       pa *= 1.0f / 12.0f;
-    } else {
-#pragma unroll
-      for (int r = 0; r < kL2; ++r) { mu[r] = 0.f; tg[r] = 0.f; }
     }
-    const uint32_t ehi0 = (uint32_t)(e0 >> 32);
     float bA = __builtin_inff(), bF = __builtin_inff();
     int kA = 0, kF = 0;
     // pass 0: this lane's draws (k = j, j + KS, ...) and their running minima,
@@ -163,24 +147,21 @@ __global__ void __launch_bounds__(kBkThreads) g2k_best_of_k_kernel(
       for (; k < kend; k += kstep) {
         const uint32_t lo = seed_lo + (uint32_t)k;         // (seed + k) mod 2^64
         const uint32_t hi = seed_hi + (lo < seed_lo ? 1u : 0u);
-        const uint32_t stream0 = gauss_stream(lo, hi, ehi0);
         float ade = 0.f, dl = 0.f;
-#pragma unroll
-        for (int t = 0; t < kL; ++t) {
-          const int64_t e = e0 + (int64_t)t * Nmax;
-          const uint32_t ehi = (uint32_t)(e >> 32);
-          uint32_t stream = stream0;
-          if (ehi != ehi0) stream = gauss_stream(lo, hi, ehi);   // a pair that straddles 2^32
-          float x, y;
-          gauss_draw(stream, (uint32_t)e, gs[t], mu[t], mu[kL + t], x, y);
+        // the stores' base, opaque to the compiler: the 24 store addresses
+        // that it otherwise forms ahead of the loop and keeps across the draws
+        // of pass 0 cost registers
+        size_t sb = pb;
+        asm volatile("" : "+v"(sb));
+        head.draw(lo, hi, e0, Nmax, mu, [&](int t, float x, float y) {
           if (pass) {
-            best[pb + (size_t)t * Nmax] = x;
-            best[pb + (size_t)(kL + t) * Nmax] = y;
+            best[sb + (size_t)t * Nmax] = x;
+            best[sb + (size_t)(kL + t) * Nmax] = y;
           }
           const float dx = x - tg[2 * t], dy = y - tg[2 * t + 1];
           dl = sqrtf(fmaf(dx, dx, dy * dy));
           ade += dl;
-        }
+        });
         ade *= 1.0f / 12.0f;
         if (!pass) {
           if (ade < bA) { bA = ade; kA = k; }              // ascending k, strict: the lowest k stays
@@ -231,6 +212,27 @@ __global__ void __launch_bounds__(256) g2k_bestk_rows_kernel(const float* __rest
   out[id] = v;
 }
 
+template <class Head>
+int best_of_k_launch_as(const g2k_dims* d, const float* pred, const float* targets,
+                        const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                        const float* head_params, uint64_t seed, int K, float* per_ped, float* best,
+                        float* out, float* rows, hipStream_t st) {
+  const BestkGeom g = bestk_geom(*d, K);
+  const int64_t wgs = (int64_t)d->S * g.C;
+  if (wgs > 0x7fffffff)
+    return set_err(G2K_EINVAL, "%sbest_of_k: %lld workgroups", Head::kPrefix, (long long)wgs);
+  hipLaunchKernelGGL(best_of_k_kernel<Head>, dim3((unsigned)wgs), dim3(kBkThreads), 0, st, pred,
+                     targets, n_active, n_frames, ped_mask, head_params, d->F, d->Nmax, g.FC, g.C,
+                     g.ks_log2, K, (uint32_t)seed, (uint32_t)(seed >> 32),
+                     (d->flags & G2K_STEP_TARGETS_SHARED) ? 1 : 0, per_ped, best,
+                     g.C == 1 ? out : rows);
+  int rc = check_launch("best_of_k_kernel");
+  if (rc || g.C == 1) return rc;
+  hipLaunchKernelGGL(g2k_bestk_rows_kernel, dim3((unsigned)(((int64_t)d->S * 8 + 255) / 256)), dim3(256),
+                     0, st, rows, d->S, g.C, K, out);
+  return check_launch("g2k_bestk_rows_kernel");
+}
+
 }  // namespace
 
 // one row [8] per (scene, chunk); FC >= 1 frame per chunk, so at most F chunks
@@ -238,23 +240,12 @@ int64_t best_of_k_ws_bytes(const g2k_dims* d) {
   return (int64_t)d->S * (d->F > 1 ? d->F : 1) * 8 * 4;
 }
 
-int best_of_k_launch(const g2k_dims* d, const float* pred, const float* targets,
+int best_of_k_launch(bool fullcov, const g2k_dims* d, const float* pred, const float* targets,
                      const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
                      const float* head, uint64_t seed, int K, float* per_ped, float* best, float* out,
                      float* rows, hipStream_t st) {
-  const BestkGeom g = bestk_geom(*d, K);
-  const int64_t wgs = (int64_t)d->S * g.C;
-  if (wgs > 0x7fffffff) return set_err(G2K_EINVAL, "best_of_k: %lld workgroups", (long long)wgs);
-  hipLaunchKernelGGL(g2k_best_of_k_kernel, dim3((unsigned)wgs), dim3(kBkThreads), 0, st, pred, targets,
-                     n_active, n_frames, ped_mask, head, d->F, d->Nmax, g.FC, g.C, g.ks_log2, K,
-                     (uint32_t)seed, (uint32_t)(seed >> 32),
-                     (d->flags & G2K_STEP_TARGETS_SHARED) ? 1 : 0, per_ped, best,
-                     g.C == 1 ? out : rows);
-  int rc = check_launch("g2k_best_of_k_kernel");
-  if (rc || g.C == 1) return rc;
-  hipLaunchKernelGGL(g2k_bestk_rows_kernel, dim3((unsigned)(((int64_t)d->S * 8 + 255) / 256)), dim3(256),
-                     0, st, rows, d->S, g.C, K, out);
-  return check_launch("g2k_bestk_rows_kernel");
+  return (fullcov ? best_of_k_launch_as<FullCovHead> : best_of_k_launch_as<PerStepHead>)(
+      d, pred, targets, n_active, n_frames, ped_mask, head, seed, K, per_ped, best, out, rows, st);
 }
 
 }  // namespace g2k

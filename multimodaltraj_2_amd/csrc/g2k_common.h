@@ -142,6 +142,17 @@ __device__ __forceinline__ float partner32(float v) {
 
 // Sum over all 64 lanes (DPP + permlane, no LDS); every lane gets the result.
 __device__ __forceinline__ float wave_sum(float v) { return sum_rows4(row16_sum(v)); }
+// ... of an int (lane shuffles)
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+// A wave-uniform value into a scalar register.
+__device__ __forceinline__ float sgpr_f(float v) {
+  return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(v)));
+}
 
 // Four per-lane values v[i] (rows 4q + i of an MFMA result, this lane's
 // column) reduced over the 16 lanes of each lane group by a transposing
@@ -202,10 +213,12 @@ __device__ __forceinline__ void error_terms(const float* y, const float* tgt, fl
 
 // ---------------------------------------------------------------------------
 // The Gaussian head's counter-based draw, shared by g2k_gauss_sample_kernel
-// (g2k_nll.hip), g2k_best_of_k_kernel (g2k_bestk.hip) and g2k_joint_kernel
-// (g2k_joint.hip) so that a draw made inside a fused evaluation is, bit for bit, the sampler's.  Restated in
-// oracle/g2k_ref.py (gauss_sample).  Every multiply-add is an explicit fmaf:
-// the bits do not depend on what the compiler contracts in either caller.
+// (g2k_nll.hip) and the per-step head's policy (PerStepHead, g2k_head_draw.h:
+// best_of_k_kernel of g2k_bestk.hip, joint_kernel and joint_wave_kernel of
+// g2k_joint.hip) so that a draw made inside a fused evaluation is, bit for
+// bit, the sampler's.  Restated in oracle/g2k_ref.py (gauss_sample).  Every
+// multiply-add is an explicit fmaf: the bits do not depend on what the
+// compiler contracts in either caller.
 //   element e = ((s * F + f) * 12 + t) * Nmax + n  (64 bit)
 //   stream    = pcg(seed_lo ^ pcg(seed_hi ^ (e >> 32)))   (the same for every
 //               element whose high word agrees: hashed once per draw index)
@@ -512,30 +525,20 @@ int nll_launch(const g2k_dims* d, const float* pred, const float* targets, const
 int gauss_sample_launch(const g2k_dims* d, const float* pred, const float* head, uint64_t seed,
                         float* out, hipStream_t st);
 
-// g2k_bestk.hip
+// g2k_bestk.hip, g2k_joint.hip: the fused evaluations of the per-step head
+// (head [3, 12]) or, with `fullcov`, of the full-covariance head (head = chol
+// [24, 24])
 int64_t best_of_k_ws_bytes(const g2k_dims* d);
-int best_of_k_launch(const g2k_dims* d, const float* pred, const float* targets,
+int best_of_k_launch(bool fullcov, const g2k_dims* d, const float* pred, const float* targets,
                      const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
                      const float* head, uint64_t seed, int K, float* per_ped, float* best, float* out,
                      float* rows, hipStream_t st);
-
-// g2k_joint.hip
 int64_t joint_eval_ws_bytes(const g2k_dims* d);
-int joint_eval_launch(const g2k_dims* d, const float* pred, const float* targets,
+int joint_eval_launch(bool fullcov, const g2k_dims* d, const float* pred, const float* targets,
                       const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
                       const float* head, uint64_t seed, int K, float radius, float* per_frame_f,
                       int32_t* per_frame_i, float* sums_f, int64_t* sums_i, int32_t* rows,
                       hipStream_t st);
-int joint_rows_launch(const g2k_dims* d, const int32_t* rows, int KD, int K, float* per_frame_f,
-                      int32_t* per_frame_i, float* sums_f, int64_t* sums_i, hipStream_t st);
-
-// g2k_fullcov_joint.hip
-int64_t fullcov_joint_eval_ws_bytes(const g2k_dims* d);
-int fullcov_joint_eval_launch(const g2k_dims* d, const float* pred, const float* targets,
-                              const int32_t* n_active, const int32_t* n_frames,
-                              const uint8_t* ped_mask, const float* chol, uint64_t seed, int K,
-                              float radius, float* per_frame_f, int32_t* per_frame_i, float* sums_f,
-                              int64_t* sums_i, int32_t* rows, hipStream_t st);
 
 // g2k_calib.hip
 int64_t head_stats_ws_bytes(const g2k_dims* d, int n_levels);
@@ -552,11 +555,6 @@ int fullcov_stats_launch(const g2k_dims* d, const float* pred, const float* targ
                          double* stats, int64_t* inside, float* fit, void* workspace, hipStream_t st);
 int fullcov_sample_launch(const g2k_dims* d, const float* pred, const float* chol, uint64_t seed,
                           float* out, hipStream_t st);
-int64_t fullcov_best_of_k_ws_bytes(const g2k_dims* d);
-int fullcov_best_of_k_launch(const g2k_dims* d, const float* pred, const float* targets,
-                             const int32_t* n_active, const int32_t* n_frames,
-                             const uint8_t* ped_mask, const float* chol, uint64_t seed, int K,
-                             float* per_ped, float* best, float* out, float* rows, hipStream_t st);
 
 // g2k_ops.hip
 int recur_launch(const float* A, float* h, int S, int frames, int D, int H, hipStream_t st);

@@ -1,8 +1,10 @@
 // g2k_fullcov.hip — the full-covariance trajectory head: ONE Gaussian over a
 // pair's whole 24-vector of residuals (the per-step head of g2k_nll.hip is its
 // block-diagonal special case).  Its closed-form fit, joint NLL and
-// calibration (g2k_fullcov_stats_f32), its sampler (g2k_fullcov_sample_f32)
-// and the fused best-of-K over its draws (g2k_fullcov_best_of_k_f32).  The
+// calibration (g2k_fullcov_stats_f32) and its sampler (g2k_fullcov_sample_f32);
+// the fused evaluations over its draws (g2k_fullcov_best_of_k_f32,
+// g2k_fullcov_joint_eval_f32) are the shared kernels of g2k_bestk.hip and
+// g2k_joint.hip with this head's policy (FullCovHead, g2k_head_draw.h).  The
 // build's: the reference has no probabilistic head, so PARITY UNPINNED;
 // tests/fullcov_ref.py restates the definition in float64 NumPy.
 //
@@ -16,9 +18,10 @@
 //   z[2t], z[2t+1] = the element's normals (gauss_normals, g2k_common.h) for
 //     e = ((s F + f) 12 + t) Nmax + n and seed (seed + k) mod 2^64
 //   draw: x[i] = mu[i] + sum_{j <= i} L[i][j] z[j], accumulated as acc = mu[i];
-//     for j = 0..i: acc = fmaf(L[i][j], z[j], acc)  (fullcov_advance: one
-//     function for the sampler and the fused best-of-K, so they agree bit for
-//     bit); written in band layout, out[c 12 + t] = x[2t + c]
+//     for j = 0..i: acc = fmaf(L[i][j], z[j], acc)  (fullcov_advance,
+//     g2k_head_draw.h: one function for the sampler and the fused evaluations,
+//     so they agree bit for bit); written in band layout, out[c 12 + t] =
+//     x[2t + c]
 //   NLL: z = L^-1 r (double), q_t = z[2t]^2 + z[2t+1]^2 (step t's innovation:
 //     chi^2(2) under a calibrated head), q = sum_t q_t (chi^2(24)),
 //     nll_t = log 2 pi + log L[2t][2t] + log L[2t+1][2t+1] + q_t / 2
@@ -29,16 +32,12 @@
 // The draw.  Row i of the product takes column j's term in ascending j, so a
 // sweep over the columns in order gives every row the defined order: after
 // step t's two normals have been added into the rows >= 2t, x[2t] and x[2t+1]
-// are final and the step's error is taken at once.  A lane holds 24 means, 24
-// running sums and 24 target coordinates; the factor (300 wave-uniform floats)
-// sits transposed in LDS (a column's entries contiguous: wide broadcast reads),
+// are final (a fused evaluation takes the step's error at once).  A lane holds
+// 24 means and 24 running sums; the factor (300 wave-uniform floats) sits
+// transposed in LDS (a column's entries contiguous: wide broadcast reads),
 // read again for every draw — each step starts with a compiler barrier so that
 // the reads are not hoisted out of the draw loop into 300 registers.  The step
 // loop is unrolled, no per-thread array is indexed at run time: no scratch.
-//
-// g2k_fullcov_best_of_k_kernel is g2k_best_of_k_kernel (g2k_bestk.hip) with
-// this draw: the same geometry (bestk_geom restated below), the same
-// lexicographic (value, k) combine, the same rows kernel's order.
 //
 // Stats.  A slot is (s, f, n), n < Nmax; the S F Nmax slots are dealt in W
 // contiguous ranges to W workgroups of 256 threads (fullcov_geom: at least
@@ -67,16 +66,16 @@
 #include <float.h>
 
 #include "g2k_common.h"
-#include "g2k_fullcov_draw.h"
+#include "g2k_head_draw.h"
 
 namespace g2k {
 namespace {
 
 // ---------------------------------------------------------------------------
-// the draw
+// the sampler
 // ---------------------------------------------------------------------------
-// fullcov_load_lt / fullcov_advance: g2k_fullcov_draw.h (shared with
-// g2k_fullcov_joint.hip)
+// fullcov_load_lt / fullcov_advance: g2k_head_draw.h (shared with the fused
+// evaluations)
 
 // one thread per (s, f, n): 24 coalesced loads along n, the 12 steps, 24 stores
 __global__ void __launch_bounds__(256) g2k_fullcov_sample_kernel(
@@ -111,195 +110,6 @@ __global__ void __launch_bounds__(256) g2k_fullcov_sample_kernel(
     out[pb + (size_t)t * Nmax] = a[2 * t];
     out[pb + (size_t)(kL + t) * Nmax] = a[2 * t + 1];
   }
-}
-
-// ---------------------------------------------------------------------------
-// fused best-of-K: g2k_best_of_k_kernel's geometry and combine, this draw
-// ---------------------------------------------------------------------------
-constexpr int kBkThreads = 256;
-constexpr int64_t kBkFill = 2 * 256 * 1024;   // items that fill 256 CUs twice over
-constexpr int kBkMaxSlices = 64;              // one wave: the combine is lane shuffles
-
-struct BestkGeom { int ks_log2, FC, C; };
-
-BestkGeom bestk_geom(const g2k_dims& d, int K) {
-  const int64_t slots = (int64_t)d.S * d.F * d.Nmax;
-  int j = 0;
-  while ((2 << j) <= K && (2 << j) <= kBkMaxSlices && (slots << j) < kBkFill) ++j;
-  int fc = kBkThreads / (d.Nmax << j);
-  if (fc > d.F) fc = d.F;
-  if (fc < 1) fc = 1;
-  BestkGeom g;
-  g.ks_log2 = j;
-  g.FC = fc;
-  g.C = d.F > 0 ? (d.F + fc - 1) / fc : 1;
-  return g;
-}
-
-__global__ void __launch_bounds__(kBkThreads) g2k_fullcov_best_of_k_kernel(
-    const float* __restrict__ pred, const float* __restrict__ targets,
-    const int32_t* __restrict__ n_active, const int32_t* __restrict__ n_frames,
-    const uint8_t* __restrict__ ped_mask, const float* __restrict__ chol, int F, int Nmax, int FC,
-    int C, int ks_log2, int K, uint32_t seed_lo, uint32_t seed_hi, int shared_targets,
-    float* __restrict__ per_ped, float* __restrict__ best, float* __restrict__ rows) {
-  __shared__ __attribute__((aligned(16))) float Lt[kL2 * kL2];
-  __shared__ float part[kBkThreads / 64][5];
-  const int tid = threadIdx.x;
-  const int s = blockIdx.x / C, c = blockIdx.x - s * C;
-  const int f0 = c * FC;
-  const int fcn = min(FC, F - f0);                         // frames of this chunk (0 when F == 0)
-  const int nact = clampi(n_active[s], 0, Nmax);
-  const int nf = n_frames ? clampi(n_frames[s], 0, F) : F;
-  const int nfc = clampi(nf - f0, 0, fcn);                 // ... of them below n_frames
-  const uint8_t* mask = ped_mask ? ped_mask + (size_t)s * Nmax : nullptr;
-
-  fullcov_load_lt(chol, Lt, tid, kBkThreads);
-  // non-pairs: zeros in per_ped, pred in best
-  if (per_ped || best) {
-    for (int idx = tid; idx < fcn * Nmax; idx += kBkThreads) {
-      const int fl = idx / Nmax, n = idx - fl * Nmax;
-      const bool pair = fl < nfc && n < nact && (mask ? mask[n] != 0 : true);
-      if (pair) continue;
-      const size_t sf = (size_t)s * F + f0 + fl;
-      if (per_ped) reinterpret_cast<float4*>(per_ped)[sf * Nmax + n] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (best) {
-        const size_t pb = sf * kL2 * Nmax + n;
-#pragma unroll
-        for (int r = 0; r < kL2; ++r) best[pb + (size_t)r * Nmax] = pred[pb + (size_t)r * Nmax];
-      }
-    }
-  }
-  __syncthreads();
-
-  const int KS = 1 << ks_log2;
-  const int j = tid & (KS - 1);                            // this lane's slice of the draws
-  const int items = (nfc * nact) << ks_log2;
-  float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int base = 0; base < items; base += kBkThreads) {   // uniform trip count
-    const int p = (base + tid) >> ks_log2;
-    const bool valid = p < nfc * nact;
-    const int fl = valid ? p / nact : 0, n = valid ? p - fl * nact : 0;
-    const bool on = valid && (mask ? mask[n] != 0 : true);
-    const size_t sf = (size_t)s * F + f0 + fl;
-    const size_t pb = sf * kL2 * Nmax + n;
-    const int64_t e0 = (int64_t)(sf * kL) * Nmax + n;      // element of step 0
-    float mu[kL2], tg[kL2];                                // both time-major: [2t + c]
-    float pa = 0.f, pf = 0.f;                              // ADE / FDE of the mean prediction
-    if (on) {
-      const size_t tf = shared_targets ? (size_t)s : sf;
-      const float2* t2 = reinterpret_cast<const float2*>(targets) + (tf * Nmax + n) * kL;
-#pragma unroll
-      for (int t = 0; t < kL; ++t) {
-        mu[2 * t] = pred[pb + (size_t)t * Nmax];
-        mu[2 * t + 1] = pred[pb + (size_t)(kL + t) * Nmax];
-        const float2 v = t2[t];
-        tg[2 * t] = v.x; tg[2 * t + 1] = v.y;
-      }
-#pragma unroll
-      for (int t = 0; t < kL; ++t) {
-        const float dx = mu[2 * t] - tg[2 * t], dy = mu[2 * t + 1] - tg[2 * t + 1];
-        pf = sqrtf(fmaf(dx, dx, dy * dy));
-        pa += pf;
-      }
-      pa *= 1.0f / 12.0f;
-    } else {
-#pragma unroll
-      for (int r = 0; r < kL2; ++r) { mu[r] = 0.f; tg[r] = 0.f; }
-    }
-    const uint32_t ehi0 = (uint32_t)(e0 >> 32);
-    float bA = __builtin_inff(), bF = __builtin_inff();
-    int kA = 0, kF = 0;
-    // pass 0: this lane's draws (k = j, j + KS, ...) and their running minima,
-    // then the slices' combine; pass 1 (best only): slice 0 makes draw kA
-    // again and stores it.  One loop body for both, so one copy of the draw.
-#pragma nounroll
-    for (int pass = 0; pass < 2; ++pass) {
-      int k = pass ? kA : j;
-      const int kend = pass ? (on && j == 0 ? kA + 1 : kA) : (on ? K : 0);
-      const int kstep = pass ? 1 : KS;
-#pragma nounroll
-      for (; k < kend; k += kstep) {
-        const uint32_t lo = seed_lo + (uint32_t)k;         // (seed + k) mod 2^64
-        const uint32_t hi = seed_hi + (lo < seed_lo ? 1u : 0u);
-        const uint32_t stream0 = gauss_stream(lo, hi, ehi0);
-        float a[kL2];
-#pragma unroll
-        for (int r = 0; r < kL2; ++r) a[r] = mu[r];
-        float ade = 0.f, dl = 0.f;
-        // the stores' base and step 0's element index, opaque to the compiler:
-        // the 24 store addresses and 12 element indices that it otherwise
-        // forms ahead of the loop and keeps across the draws of pass 0 cost
-        // ~65 registers (the indices are 32-bit here: t Nmax < 2^32, so the
-        // high word moves at most once, by a carry)
-        size_t sb = pb;
-        uint32_t elo0 = (uint32_t)e0;
-        asm volatile("" : "+v"(sb), "+v"(elo0));
-#pragma unroll
-        for (int t = 0; t < kL; ++t) {
-          const uint32_t elo = elo0 + (uint32_t)(t * Nmax);
-          uint32_t stream = stream0;
-          if (elo < elo0) stream = gauss_stream(lo, hi, ehi0 + 1u);   // a pair that straddles 2^32
-          float z0, z1;
-          gauss_normals(stream, elo, z0, z1);
-          fullcov_advance(Lt, t, z0, z1, a);
-          const float x = a[2 * t], y = a[2 * t + 1];
-          if (pass) {
-            best[sb + (size_t)t * Nmax] = x;
-            best[sb + (size_t)(kL + t) * Nmax] = y;
-          }
-          const float dx = x - tg[2 * t], dy = y - tg[2 * t + 1];
-          dl = sqrtf(fmaf(dx, dx, dy * dy));
-          ade += dl;
-        }
-        ade *= 1.0f / 12.0f;
-        if (!pass) {
-          if (ade < bA) { bA = ade; kA = k; }              // ascending k, strict: the lowest k stays
-          if (dl < bF) { bF = dl; kF = k; }
-        }
-      }
-      if (pass) break;
-      for (int off = 1; off < KS; off <<= 1) {             // every lane takes part
-        const float oA = __shfl_xor(bA, off), oF = __shfl_xor(bF, off);
-        const int okA = __shfl_xor(kA, off), okF = __shfl_xor(kF, off);
-        if (oA < bA || (oA == bA && okA < kA)) { bA = oA; kA = okA; }
-        if (oF < bF || (oF == bF && okF < kF)) { bF = oF; kF = okF; }
-      }
-      if (!best) break;
-    }
-    if (on && j == 0) {
-      if (per_ped)
-        reinterpret_cast<float4*>(per_ped)[sf * Nmax + n] = make_float4(bA, bF, (float)kA, (float)kF);
-      acc[0] += bA; acc[1] += bF; acc[2] += 1.f; acc[3] += pa; acc[4] += pf;
-    }
-  }
-  // the workgroup's row: lanes by butterfly, waves in order
-#pragma unroll
-  for (int i = 0; i < 5; ++i) {
-    const float v = wave_sum(acc[i]);
-    if ((tid & 63) == 0) part[tid >> 6][i] = v;
-  }
-  __syncthreads();
-  if (tid < 8) {
-    float v = 0.f;
-    if (tid < 5) v = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
-    if (tid == 5) v = (float)K;
-    rows[(size_t)blockIdx.x * 8 + tid] = v;
-  }
-}
-
-// out[s][i] = sum over the scene's C chunk rows, in chunk order
-__global__ void __launch_bounds__(256) g2k_fullcov_bestk_rows_kernel(const float* __restrict__ rows,
-                                                                     int S, int C, int K,
-                                                                     float* __restrict__ out) {
-  const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (id >= (int64_t)S * 8) return;
-  const int64_t s = id >> 3;
-  const int i = (int)(id & 7);
-  float v = 0.f;
-  if (i < 5)
-    for (int c = 0; c < C; ++c) v += rows[((size_t)s * C + c) * 8 + i];
-  if (i == 5) v = (float)K;
-  out[id] = v;
 }
 
 // ---------------------------------------------------------------------------
@@ -685,31 +495,6 @@ int fullcov_sample_launch(const g2k_dims* d, const float* pred, const float* cho
   hipLaunchKernelGGL(g2k_fullcov_sample_kernel, dim3((unsigned)wgs), dim3(256), 0, st, pred, chol, slots,
                      d->Nmax, (uint32_t)seed, (uint32_t)(seed >> 32), out);
   return check_launch("g2k_fullcov_sample_kernel");
-}
-
-// one row [8] per (scene, chunk); FC >= 1 frame per chunk, so at most F chunks
-int64_t fullcov_best_of_k_ws_bytes(const g2k_dims* d) {
-  return (int64_t)d->S * (d->F > 1 ? d->F : 1) * 8 * 4;
-}
-
-int fullcov_best_of_k_launch(const g2k_dims* d, const float* pred, const float* targets,
-                             const int32_t* n_active, const int32_t* n_frames,
-                             const uint8_t* ped_mask, const float* chol, uint64_t seed, int K,
-                             float* per_ped, float* best, float* out, float* rows, hipStream_t st) {
-  const BestkGeom g = bestk_geom(*d, K);
-  const int64_t wgs = (int64_t)d->S * g.C;
-  if (wgs > 0x7fffffff)
-    return set_err(G2K_EINVAL, "fullcov_best_of_k: %lld workgroups", (long long)wgs);
-  hipLaunchKernelGGL(g2k_fullcov_best_of_k_kernel, dim3((unsigned)wgs), dim3(kBkThreads), 0, st, pred,
-                     targets, n_active, n_frames, ped_mask, chol, d->F, d->Nmax, g.FC, g.C, g.ks_log2, K,
-                     (uint32_t)seed, (uint32_t)(seed >> 32),
-                     (d->flags & G2K_STEP_TARGETS_SHARED) ? 1 : 0, per_ped, best,
-                     g.C == 1 ? out : rows);
-  int rc = check_launch("g2k_fullcov_best_of_k_kernel");
-  if (rc || g.C == 1) return rc;
-  hipLaunchKernelGGL(g2k_fullcov_bestk_rows_kernel, dim3((unsigned)(((int64_t)d->S * 8 + 255) / 256)),
-                     dim3(256), 0, st, rows, d->S, g.C, K, out);
-  return check_launch("g2k_fullcov_bestk_rows_kernel");
 }
 
 }  // namespace g2k

@@ -1,0 +1,174 @@
+// g2k_head_draw.h — the two probabilistic heads as device-side policies: what
+// the fused evaluations (best_of_k_kernel, g2k_bestk.hip; joint_kernel and
+// joint_wave_kernel, g2k_joint.hip) take as their template parameter.  A
+// policy owns exactly what differs between the heads:
+//   Lds                       what it keeps in LDS for the workgroup
+//   stage(p, lds, tid, n)     fills it from the head's parameters, n threads
+//                             taking part (the caller's barrier follows)
+//   bind(lds)                 what a lane then draws from
+//   draw(lo, hi, e0, Nmax, mu, step)
+//                             one draw of one member for seed (hi, lo), whose
+//                             step-0 element is e0 and whose means are mu
+//                             (time-major, mu[2t + c]); calls step(t, x, y) as
+//                             soon as step t's two coordinates are final
+//   kPrefix                   the head's prefix in a launcher's messages
+//   kJointWaveOccupancy       joint_wave_kernel's amdgpu_waves_per_eu (1: no
+//                             hint, the compiler's default)
+// Each draw is the code of its head's sampler (gauss_draw, g2k_common.h, and
+// g2k_gauss_sample_kernel; fullcov_advance below and g2k_fullcov_sample_kernel),
+// so that a draw made inside a fused evaluation is, bit for bit, the sampler's.
+#pragma once
+#include "g2k_common.h"
+
+namespace g2k {
+namespace {
+
+// ---------------------------------------------------------------------------
+// the per-step bivariate-Gaussian head (g2k_nll.hip): head [3, 12]
+// ---------------------------------------------------------------------------
+struct PerStepHead {
+  static constexpr const char* kPrefix = "";
+  static constexpr int kJointWaveOccupancy = 1;
+  struct Lds { float4 hs[kL]; };       // per step {sigma_x, sigma_y, rho, sqrt(1 - rho^2)}
+  GaussStep gs[kL];                    // wave-uniform: scalar registers
+
+  static __device__ __forceinline__ void stage(const float* __restrict__ head, Lds& lds, int tid,
+                                               int nthreads) {
+    for (int t = tid; t < kL; t += nthreads) {
+      const GaussStep g = gauss_step(head, t);
+      lds.hs[t] = make_float4(g.sx, g.sy, g.rho, g.sq);
+    }
+  }
+  __device__ __forceinline__ void bind(const Lds& lds) {
+#pragma unroll
+    for (int t = 0; t < kL; ++t) {
+      const float4 v = lds.hs[t];
+      gs[t].sx = sgpr_f(v.x); gs[t].sy = sgpr_f(v.y); gs[t].rho = sgpr_f(v.z); gs[t].sq = sgpr_f(v.w);
+    }
+  }
+  template <class Step>
+  __device__ __forceinline__ void draw(uint32_t lo, uint32_t hi, int64_t e0, int Nmax,
+                                       const float (&mu)[kL2], Step&& step) const {
+    const uint32_t ehi0 = (uint32_t)(e0 >> 32);
+    const uint32_t stream0 = gauss_stream(lo, hi, ehi0);
+#pragma unroll
+    for (int t = 0; t < kL; ++t) {
+      const int64_t e = e0 + (int64_t)t * Nmax;
+      const uint32_t ehi = (uint32_t)(e >> 32);
+      uint32_t stream = stream0;
+      if (ehi != ehi0) stream = gauss_stream(lo, hi, ehi);   // a member that straddles 2^32
+      float x, y;
+      gauss_draw(stream, (uint32_t)e, gs[t], mu[2 * t], mu[2 * t + 1], x, y);
+      step(t, x, y);
+    }
+  }
+};
+
+// ---------------------------------------------------------------------------
+// the full-covariance trajectory head (g2k_fullcov.hip holds the definition):
+// chol [24][24], the lower Cholesky factor over the coordinates i = 2t + c
+// ---------------------------------------------------------------------------
+// Lt (LDS) = the factor transposed: Lt[j * 24 + i] = L[i][j], j <= i (entries
+// above the diagonal are not read from memory)
+__device__ __forceinline__ void fullcov_load_lt(const float* __restrict__ chol, float* Lt, int tid,
+                                                int nthreads) {
+  for (int idx = tid; idx < kL2 * kL2; idx += nthreads) {
+    const int i = idx / kL2, j = idx - i * kL2;
+    float v = 0.f;
+    if (j <= i) v = chol[idx];
+    Lt[j * kL2 + i] = v;
+  }
+}
+
+// step t of a draw: column 2t's terms into the rows >= 2t, then column 2t+1's
+// into the rows >= 2t+1; a[2t], a[2t+1] are final afterwards (t a constant
+// after unrolling: every index is one)
+__device__ __forceinline__ void fullcov_advance(const float* Lt, int t, float z0, float z1,
+                                                float (&a)[kL2]) {
+  // a step's columns are read when the step is reached: the compiler may not
+  // gather the 300 reads of a draw ahead of the draw loop
+  asm volatile("" ::: "memory");
+#pragma unroll
+  for (int i = 0; i < kL2; ++i)
+    if (i >= 2 * t) a[i] = fmaf(Lt[(2 * t) * kL2 + i], z0, a[i]);
+#pragma unroll
+  for (int i = 0; i < kL2; ++i)
+    if (i >= 2 * t + 1) a[i] = fmaf(Lt[(2 * t + 1) * kL2 + i], z1, a[i]);
+}
+
+// The draw: row i of the product takes column j's term in ascending j, so a
+// sweep over the columns in order gives every row the defined order; the 24
+// running sums start as the means, and after step t's two normals have been
+// added into the rows >= 2t, a[2t] and a[2t+1] are final.  The factor (300
+// wave-uniform floats) is read from LDS again for every draw by broadcast
+// reads.  The step loop is unrolled, no per-thread array is indexed at run
+// time: no scratch.
+struct FullCovHead {
+  static constexpr const char* kPrefix = "fullcov_";
+  static constexpr int kJointWaveOccupancy = 2;
+  struct alignas(16) Lds { float Lt[kL2 * kL2]; };
+  const float* Lt;
+
+  static __device__ __forceinline__ void stage(const float* __restrict__ chol, Lds& lds, int tid,
+                                               int nthreads) {
+    fullcov_load_lt(chol, lds.Lt, tid, nthreads);
+  }
+  __device__ __forceinline__ void bind(const Lds& lds) { Lt = lds.Lt; }
+  template <class Step>
+  __device__ __forceinline__ void draw(uint32_t lo, uint32_t hi, int64_t e0, int Nmax,
+                                       const float (&mu)[kL2], Step&& step) const {
+    const uint32_t ehi0 = (uint32_t)(e0 >> 32);
+    const uint32_t stream0 = gauss_stream(lo, hi, ehi0);
+    float a[kL2];
+#pragma unroll
+    for (int r = 0; r < kL2; ++r) a[r] = mu[r];
+    // step 0's element index, opaque to the compiler: the 12 indices (and the
+    // 12 straddle tests) that it otherwise forms ahead of the draw loop and
+    // keeps across it cost registers (the indices are 32-bit here: t Nmax <
+    // 2^32, so the high word moves at most once, by a carry)
+    uint32_t elo0 = (uint32_t)e0;
+    asm volatile("" : "+v"(elo0));
+#pragma unroll
+    for (int t = 0; t < kL; ++t) {
+      const uint32_t elo = elo0 + (uint32_t)(t * Nmax);
+      uint32_t stream = stream0;
+      if (elo < elo0) stream = gauss_stream(lo, hi, ehi0 + 1u);   // a member that straddles 2^32
+      float z0, z1;
+      gauss_normals(stream, elo, z0, z1);
+      fullcov_advance(Lt, t, z0, z1, a);
+      // the step's sums are formed in the step: without this the compiler sinks
+      // the later rows' FMAs past the following steps' (branching) sin / cos to
+      // where the rows are used, and keeps the 300 values read from Lt (which
+      // cannot move) in registers until then — 256 VGPRs + 219 AGPRs in the
+      // joint kernels
+#pragma unroll
+      for (int i = 2 * t + 2; i < kL2; ++i) asm volatile("" : "+v"(a[i]));
+      step(t, a[2 * t], a[2 * t + 1]);
+    }
+  }
+};
+
+// A pair's (a member's) 24 means and 24 target coordinates, both time-major
+// ([2t + c]: the indices are constants after unrolling, so the order is one
+// of names only); zeros for a lane that is off.
+__device__ __forceinline__ void load_mu_tg(bool on, const float* __restrict__ pred,
+                                           const float* __restrict__ targets, size_t sf, size_t tf,
+                                           int n, int Nmax, float (&mu)[kL2], float (&tg)[kL2]) {
+  if (on) {
+    const size_t pb = sf * kL2 * Nmax + n;
+    const float2* t2 = reinterpret_cast<const float2*>(targets) + (tf * Nmax + n) * kL;
+#pragma unroll
+    for (int t = 0; t < kL; ++t) {
+      mu[2 * t] = pred[pb + (size_t)t * Nmax];
+      mu[2 * t + 1] = pred[pb + (size_t)(kL + t) * Nmax];
+      const float2 v = t2[t];
+      tg[2 * t] = v.x; tg[2 * t + 1] = v.y;
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < kL2; ++r) { mu[r] = 0.f; tg[r] = 0.f; }
+  }
+}
+
+}  // namespace
+}  // namespace g2k

@@ -1,17 +1,23 @@
-// g2k_joint.hip — fused JOINT best-of-K evaluation of the bivariate-Gaussian
-// head: JADE_K / JFDE_K (one draw index for the whole scene-frame) and the
-// collision counts of the draws, of the mean prediction and of the targets.
-// The build's: the reference has no probabilistic head, so PARITY UNPINNED;
-// tests/joint_ref.py restates the definition over oracle/g2k_ref.py
-// gauss_sample and tests/bestk_ref.py.
+// g2k_joint.hip — fused JOINT best-of-K evaluation of a probabilistic head:
+// JADE_K / JFDE_K (one draw index for the whole scene-frame) and the collision
+// counts of the draws, of the mean prediction and of the targets.  ONE pair of
+// kernels, joint_kernel<Head> and joint_wave_kernel<Head>, instantiated for
+// the per-step bivariate-Gaussian head (g2k_joint_eval_f32) and for the
+// full-covariance trajectory head (g2k_fullcov_joint_eval_f32); the heads are
+// the policies of g2k_head_draw.h.  The build's: the reference has no
+// probabilistic head, so PARITY UNPINNED; tests/joint_ref.py restates the
+// definition over oracle/g2k_ref.py gauss_sample and tests/bestk_ref.py,
+// tests/fullcov_joint_ref.py over tests/fullcov_ref.py.
 //
 // Definition.  Inputs as g2k_best_of_k_f32 (g2k_bestk.hip) plus radius
 // (finite, >= 0).  The MEMBERS of scene-frame (s, f), f < n_frames[s], are the
 // n with n < n_active[s] and ped_mask[s][n] != 0 (the pairs of g2k_bestk.hip);
 // P their number, PP = P (P - 1) / 2 the unordered member couples.
-//   joint sample k (k < K) = for every member what g2k_gauss_sample_f32 writes
-//     for seed (seed + k) mod 2^64 (gauss_draw, g2k_common.h: the sampler's
-//     bits, the draws g2k_best_of_k_f32 sees)
+//   joint sample k (k < K) = for every member what the head's sampler
+//     (g2k_gauss_sample_f32, g2k_fullcov_sample_f32) writes for seed
+//     (seed + k) mod 2^64: the sampler's bits, the draws the head's marginal
+//     best-of-K sees (a member whose element counter straddles 2^32 re-keyed
+//     as there; entries of chol above the diagonal are never read)
 //   JADE_k = mean over members of ADE_k, JFDE_k = mean over members of FDE_k
 //     (ADE_k / FDE_k as in g2k_bestk.hip); minJADE / minJFDE taken
 //     independently, kJA / kJF the lowest k attaining each
@@ -32,15 +38,16 @@
 // the shapes alone (joint_geom): enough units to fill the device (2048 waves /
 // 512 workgroups), at most 8, and at least two draws per unit so that a unit's
 // set-up (compaction, 24 means and 24 target coordinates per member into
-// registers) is shared.  The unit first compacts its members (ballot + prefix
-// count): non-members never reach the hash or the pair loop.  Its ITEMS are,
-// for slice 0, the targets and the mean prediction (col_gt, col_pred), then
-// for every slice its draws.  An item's sample is written to LDS as xy[i][24]
-// (12 x, 12 y: six 16-byte reads fetch a whole member) — no draw reaches
-// global memory — and paired all-against-all from there: a lane keeps member
-// i's 24 coordinates in registers, all lanes that share a sample read the same
-// member j (one LDS address: a broadcast), and count i < j only.
-//   Nmax > 64 (g2k_joint_kernel; dense_crowd, P up to 256): four waves per
+// registers, both time-major, [2t + c]) is shared.  The unit first compacts
+// its members (ballot + prefix count): non-members never reach the hash or the
+// pair loop.  Its ITEMS are, for slice 0, the targets and the mean prediction
+// (col_gt, col_pred), then for every slice its draws.  An item's sample is
+// written to LDS as xy[i][24] (12 x, 12 y: six 16-byte reads fetch a whole
+// member) — no draw reaches global memory — and paired all-against-all from
+// there: a lane keeps member i's 24 coordinates in registers, all lanes that
+// share a sample read the same member j (one LDS address: a broadcast), and
+// count i < j only.
+//   Nmax > 64 (joint_kernel; dense_crowd, P up to 256): four waves per
 // unit, thread i owns member i, one item per pass.  The draw's ADE / FDE sums
 // go lanes-by-butterfly, waves-in-order.  The pair pass walks 64-row x
 // 32-column tiles of the upper triangle, dealt round-robin to the waves.  The
@@ -48,7 +55,7 @@
 // one barrier per pass: waves that finish their tiles early draw the next
 // sample while the others still count.  A pass's collision total is read one
 // barrier later (the same parity argument).
-//   Nmax <= 64 (g2k_joint_wave_kernel; real-data evaluation: F 1, hundreds of
+//   Nmax <= 64 (joint_wave_kernel; real-data evaluation: F 1, hundreds of
 // scenes, P 2..32): one wave per unit, cut into 64 / GL groups of GL = 16, 32
 // or 64 lanes (the smallest that holds P); every group takes another item in
 // the same pass, so a small scene-frame still fills the wave.
@@ -60,55 +67,122 @@
 // and, JADE_k being computed the same way in whichever unit draws k, do not
 // depend on KD.
 #include "g2k_common.h"
-#include "g2k_joint.h"
+#include "g2k_head_draw.h"
 
 namespace g2k {
 namespace {
 
-// joint_geom, the row format, pair_pass: g2k_joint.h (shared with
-// g2k_fullcov_joint.hip)
+constexpr int kJtMaxDeal = 8;        // units per scene-frame at most
+constexpr int kJtRow = 10;           // int32 words per unit row
+constexpr int kJtTileJ = 32;         // columns (j) per pair-pass tile
+constexpr int kJtWaves = 4;          // waves of a unit when Nmax > 64
 
-// One member's 24 coordinates of a pass (x[12], y[12]): kind 1 the targets,
-// kind 2 the mean, kind 3 draw k with its ADE / FDE against the targets.
-__device__ __forceinline__ void joint_coords(int kind, int k, const float* mu, const float* tg,
-                                             const GaussStep* gs, int64_t e0, int Nmax,
-                                             uint32_t seed_lo, uint32_t seed_hi, float* c, float& ade,
-                                             float& fde) {
+struct JointGeom { int waves, KD; };
+
+int joint_kd_max(const g2k_dims& d) {
+  const int64_t sf = (int64_t)d.S * d.F;
+  const int64_t fill = d.Nmax <= 64 ? 2048 : 512;      // waves / workgroups that fill 256 CUs
+  int64_t kd = sf > 0 ? (fill + sf - 1) / sf : 1;
+  if (kd > kJtMaxDeal) kd = kJtMaxDeal;
+  return (int)kd;
+}
+
+JointGeom joint_geom(const g2k_dims& d, int K) {
+  JointGeom g;
+  g.waves = d.Nmax <= 64 ? 1 : kJtWaves;
+  g.KD = joint_kd_max(d);
+  const int two = (K + 1) / 2;                          // >= 2 draws per unit (K = 1: one unit)
+  if (g.KD > two) g.KD = two;
+  return g;
+}
+
+// Collisions of the LDS sample `buf` (xy[i][24], P members) among this wave's
+// tiles: tile (b, c) = rows 64 b .. 64 b + 63 x columns 32 c .. 32 c + 31,
+// c >= 2 b (the upper triangle), tile number % kJtWaves == w.
+__device__ __forceinline__ int pair_pass(const float4* __restrict__ buf, int P, int w, int lane,
+                                         float r2) {
+  const int NB = (P + 63) >> 6, NC = (P + kJtTileJ - 1) / kJtTileJ;
+  int cnt = 0, tix = 0;
+  for (int b = 0; b < NB; ++b) {
+    bool loaded = false;
+    float xi[kL], yi[kL];
+    const int i = (b << 6) + lane;
+    for (int c = 2 * b; c < NC; ++c, ++tix) {
+      if ((tix & (kJtWaves - 1)) != w) continue;
+      if (!loaded) {                                      // this row block's coordinates
+        const float4* pi = buf + (size_t)min(i, P - 1) * 6;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+          const float4 a = pi[q], bq = pi[3 + q];
+          xi[4 * q] = a.x; xi[4 * q + 1] = a.y; xi[4 * q + 2] = a.z; xi[4 * q + 3] = a.w;
+          yi[4 * q] = bq.x; yi[4 * q + 1] = bq.y; yi[4 * q + 2] = bq.z; yi[4 * q + 3] = bq.w;
+        }
+        loaded = true;
+      }
+      const int j0 = max(c * kJtTileJ, (b << 6) + 1), j1 = min((c + 1) * kJtTileJ, P);
+      for (int j = j0; j < j1; ++j) {                     // uniform: every lane reads member j
+        const float4* pj = buf + (size_t)j * 6;
+        float m = __builtin_inff();
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+          const float4 a = pj[q], bq = pj[3 + q];
+          const float xj[4] = {a.x, a.y, a.z, a.w}, yj[4] = {bq.x, bq.y, bq.z, bq.w};
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const float dx = xi[4 * q + u] - xj[u], dy = yi[4 * q + u] - yj[u];
+            m = fminf(m, fmaf(dx, dx, dy * dy));
+          }
+        }
+        cnt += (i < j && m < r2) ? 1 : 0;                 // rows >= P: i < j never holds
+      }
+    }
+  }
+  return cnt;
+}
+
+// One member's 24 coordinates of a pass, time-major (c[2t] = x, c[2t+1] = y):
+// kind 1 the targets, kind 2 the mean, kind 3 draw k with its ADE / FDE
+// against the targets (step t's term is taken as soon as the step is final).
+template <class Head>
+__device__ __forceinline__ void joint_coords(const Head& head, int kind, int k, const float (&mu)[kL2],
+                                             const float (&tg)[kL2], int64_t e0, int Nmax,
+                                             uint32_t seed_lo, uint32_t seed_hi, float (&c)[kL2],
+                                             float& ade, float& fde) {
   if (kind != 3) {
 #pragma unroll
-    for (int t = 0; t < kL; ++t) {
-      c[t] = kind == 1 ? tg[2 * t] : mu[t];
-      c[kL + t] = kind == 1 ? tg[2 * t + 1] : mu[kL + t];
-    }
+    for (int r = 0; r < kL2; ++r) c[r] = kind == 1 ? tg[r] : mu[r];
     return;
   }
-  const uint32_t ehi0 = (uint32_t)(e0 >> 32);
   const uint32_t lo = seed_lo + (uint32_t)k;               // (seed + k) mod 2^64
   const uint32_t hi = seed_hi + (lo < seed_lo ? 1u : 0u);
-  const uint32_t stream0 = gauss_stream(lo, hi, ehi0);
-#pragma unroll
-  for (int t = 0; t < kL; ++t) {
-    const int64_t e = e0 + (int64_t)t * Nmax;
-    const uint32_t ehi = (uint32_t)(e >> 32);
-    uint32_t stream = stream0;
-    if (ehi != ehi0) stream = gauss_stream(lo, hi, ehi);   // a member that straddles 2^32
-    gauss_draw(stream, (uint32_t)e, gs[t], mu[t], mu[kL + t], c[t], c[kL + t]);
-    const float dx = c[t] - tg[2 * t], dy = c[kL + t] - tg[2 * t + 1];
+  head.draw(lo, hi, e0, Nmax, mu, [&](int t, float x, float y) {
+    c[2 * t] = x; c[2 * t + 1] = y;
+    const float dx = x - tg[2 * t], dy = y - tg[2 * t + 1];
     fde = sqrtf(fmaf(dx, dx, dy * dy));
     ade += fde;
-  }
+  });
   ade *= 1.0f / 12.0f;
 }
 
-__global__ void __launch_bounds__(kJtWaves * 64) g2k_joint_kernel(
+// time-major c -> xy[i][24] = 12 x, then 12 y
+__device__ __forceinline__ void joint_store(float4* dst, const float (&c)[kL2]) {
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    dst[r] = make_float4(c[8 * r], c[8 * r + 2], c[8 * r + 4], c[8 * r + 6]);
+    dst[3 + r] = make_float4(c[8 * r + 1], c[8 * r + 3], c[8 * r + 5], c[8 * r + 7]);
+  }
+}
+
+template <class Head>
+__global__ void __launch_bounds__(kJtWaves * 64) joint_kernel(
     const float* __restrict__ pred, const float* __restrict__ targets,
     const int32_t* __restrict__ n_active, const int32_t* __restrict__ n_frames,
-    const uint8_t* __restrict__ ped_mask, const float* __restrict__ head, int F, int Nmax, int KD,
-    int K, uint32_t seed_lo, uint32_t seed_hi, int shared_targets, float r2,
+    const uint8_t* __restrict__ ped_mask, const float* __restrict__ head_params, int F, int Nmax,
+    int KD, int K, uint32_t seed_lo, uint32_t seed_hi, int shared_targets, float r2,
     int32_t* __restrict__ rows) {
   constexpr int WAVES = kJtWaves, NBUF = 2;
   constexpr int CAP = WAVES * 64;                          // members a unit holds (>= Nmax)
-  __shared__ float4 hs[kL];
+  __shared__ typename Head::Lds hlds;
   __shared__ float4 xy[NBUF][CAP * 6];
   __shared__ float jpart[NBUF][WAVES][2];
   __shared__ int cpart[NBUF][WAVES];
@@ -122,10 +196,7 @@ __global__ void __launch_bounds__(kJtWaves * 64) g2k_joint_kernel(
   const int nf = n_frames ? clampi(n_frames[s], 0, F) : F;
   int32_t* row = rows + (size_t)blockIdx.x * kJtRow;
 
-  if (tid < kL) {
-    const GaussStep g = gauss_step(head, tid);
-    hs[tid] = make_float4(g.sx, g.sy, g.rho, g.sq);
-  }
+  Head::stage(head_params, hlds, tid, CAP);
   // compact the members: thread i owns member i = column midx[i]
   bool mem = f < nf && tid < nact;
   if (mem && ped_mask) mem = ped_mask[(size_t)s * Nmax + tid] != 0;
@@ -146,33 +217,15 @@ __global__ void __launch_bounds__(kJtWaves * 64) g2k_joint_kernel(
     if (tid < kJtRow) row[tid] = 0;
     return;
   }
-  GaussStep gs[kL];                                        // wave-uniform: scalar registers
-#pragma unroll
-  for (int t = 0; t < kL; ++t) {
-    const float4 v = hs[t];
-    gs[t].sx = sgpr_f(v.x); gs[t].sy = sgpr_f(v.y); gs[t].rho = sgpr_f(v.z); gs[t].sq = sgpr_f(v.w);
-  }
+  Head head;
+  head.bind(hlds);
 
   const bool on = tid < P;
   const int n = on ? midx[tid] : 0;
   const size_t sf = (size_t)sfi;
-  const size_t pb = sf * kL2 * Nmax + n;
   const int64_t e0 = (int64_t)(sf * kL) * Nmax + n;        // element of step 0
   float mu[kL2], tg[kL2];
-  if (on) {
-    const size_t tf = shared_targets ? (size_t)s : sf;
-    const float2* t2 = reinterpret_cast<const float2*>(targets) + (tf * Nmax + n) * kL;
-#pragma unroll
-    for (int t = 0; t < kL; ++t) {
-      mu[t] = pred[pb + (size_t)t * Nmax];
-      mu[kL + t] = pred[pb + (size_t)(kL + t) * Nmax];
-      const float2 v = t2[t];
-      tg[2 * t] = v.x; tg[2 * t + 1] = v.y;
-    }
-  } else {
-#pragma unroll
-    for (int r = 0; r < kL2; ++r) { mu[r] = 0.f; tg[r] = 0.f; }
-  }
+  load_mu_tg(on, pred, targets, sf, shared_targets ? (size_t)s : sf, n, Nmax, mu, tg);
 
   // passes: slice 0 first counts the targets (kind 1) and the mean (kind 2);
   // then the slice's draws k = sl, sl + KD, ... (kind 3; 4 once it is the
@@ -198,13 +251,11 @@ __global__ void __launch_bounds__(kJtWaves * 64) g2k_joint_kernel(
     const int par = q & (NBUF - 1);
     const int kind = q < npre ? q + 1 : 3;
     const int k = sl + (q - npre) * KD;
-    float c[kL2];
     float ade = 0.f, fde = 0.f;
     if (on) {
-      joint_coords(kind, k, mu, tg, gs, e0, Nmax, seed_lo, seed_hi, c, ade, fde);
-      float4* dst = &xy[par][(size_t)tid * 6];
-#pragma unroll
-      for (int r = 0; r < 6; ++r) dst[r] = make_float4(c[4 * r], c[4 * r + 1], c[4 * r + 2], c[4 * r + 3]);
+      float c[kL2];
+      joint_coords(head, kind, k, mu, tg, e0, Nmax, seed_lo, seed_hi, c, ade, fde);
+      joint_store(&xy[par][(size_t)tid * 6], c);
     }
     if (kind == 3) {                                       // every lane takes part in the butterfly
       const float sa = wave_sum(ade), sfd = wave_sum(fde);
@@ -242,14 +293,22 @@ __global__ void __launch_bounds__(kJtWaves * 64) g2k_joint_kernel(
 // of a group read the same column j (one address per group; the groups' samples
 // start 16 bytes off a multiple of the bank cycle, so their reads do not
 // collide), sums run over the group's lanes by an xor butterfly.  The groups'
-// results are merged like the units' (lexicographic minima, integer sums).
-__global__ void __launch_bounds__(64) g2k_joint_wave_kernel(
+// results are merged like the units' (lexicographic minima, integer sums).  The
+// groups draw different k from the same head: what they read of it in LDS is
+// the same address in every lane.  The occupancy hint is the head's
+// (kJointWaveOccupancy): without it the allocator settles the full-covariance
+// instantiation at 256 VGPRs + 1 AGPR, one register over two waves per SIMD;
+// with it 256 + 0, scratch 0, nothing spilled.  The per-step instantiation
+// runs without one (205 VGPRs): with the hint it came out at 191 VGPRs and
+// 1.8 us slower at the real-data evaluation's shape (51.8 -> 53.6 us).
+template <class Head>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Head::kJointWaveOccupancy))) joint_wave_kernel(
     const float* __restrict__ pred, const float* __restrict__ targets,
     const int32_t* __restrict__ n_active, const int32_t* __restrict__ n_frames,
-    const uint8_t* __restrict__ ped_mask, const float* __restrict__ head, int F, int Nmax, int KD,
-    int K, uint32_t seed_lo, uint32_t seed_hi, int shared_targets, float r2,
+    const uint8_t* __restrict__ ped_mask, const float* __restrict__ head_params, int F, int Nmax,
+    int KD, int K, uint32_t seed_lo, uint32_t seed_hi, int shared_targets, float r2,
     int32_t* __restrict__ rows) {
-  __shared__ float4 hs[kL];
+  __shared__ typename Head::Lds hlds;
   __shared__ float4 xy[64 * 6 + 4];
   __shared__ int midx[64];
   const int lane = threadIdx.x;
@@ -259,10 +318,7 @@ __global__ void __launch_bounds__(64) g2k_joint_wave_kernel(
   const int nf = n_frames ? clampi(n_frames[s], 0, F) : F;
   int32_t* row = rows + (size_t)blockIdx.x * kJtRow;
 
-  if (lane < kL) {
-    const GaussStep g = gauss_step(head, lane);
-    hs[lane] = make_float4(g.sx, g.sy, g.rho, g.sq);
-  }
+  Head::stage(head_params, hlds, lane, 64);
   bool mem = f < nf && lane < nact;                        // Nmax <= 64: lane n looks at column n
   if (mem && ped_mask) mem = ped_mask[(size_t)s * Nmax + lane] != 0;
   const unsigned long long bal = __ballot(mem);
@@ -273,12 +329,8 @@ __global__ void __launch_bounds__(64) g2k_joint_wave_kernel(
     if (lane < kJtRow) row[lane] = 0;
     return;
   }
-  GaussStep gs[kL];                                        // wave-uniform: scalar registers
-#pragma unroll
-  for (int t = 0; t < kL; ++t) {
-    const float4 v = hs[t];
-    gs[t].sx = sgpr_f(v.x); gs[t].sy = sgpr_f(v.y); gs[t].rho = sgpr_f(v.z); gs[t].sq = sgpr_f(v.w);
-  }
+  Head head;
+  head.bind(hlds);
 
   const int gl2 = P <= 16 ? 4 : (P <= 32 ? 5 : 6);         // log2 of the lanes per group
   const int GL = 1 << gl2, G = 64 >> gl2;
@@ -286,23 +338,9 @@ __global__ void __launch_bounds__(64) g2k_joint_wave_kernel(
   const bool on = i < P;
   const int n = on ? midx[i] : 0;
   const size_t sf = (size_t)sfi;
-  const size_t pb = sf * kL2 * Nmax + n;
   const int64_t e0 = (int64_t)(sf * kL) * Nmax + n;        // element of step 0
   float mu[kL2], tg[kL2];
-  if (on) {
-    const size_t tf = shared_targets ? (size_t)s : sf;
-    const float2* t2 = reinterpret_cast<const float2*>(targets) + (tf * Nmax + n) * kL;
-#pragma unroll
-    for (int t = 0; t < kL; ++t) {
-      mu[t] = pred[pb + (size_t)t * Nmax];
-      mu[kL + t] = pred[pb + (size_t)(kL + t) * Nmax];
-      const float2 v = t2[t];
-      tg[2 * t] = v.x; tg[2 * t + 1] = v.y;
-    }
-  } else {
-#pragma unroll
-    for (int r = 0; r < kL2; ++r) { mu[r] = 0.f; tg[r] = 0.f; }
-  }
+  load_mu_tg(on, pred, targets, sf, shared_targets ? (size_t)s : sf, n, Nmax, mu, tg);
   float4* mine = xy + g * (GL * 6 + 1);                    // the group's sample: at most 386 + 1 < 388
 
   // items: slice 0 begins with the targets (kind 1) and the mean (kind 2),
@@ -321,10 +359,8 @@ __global__ void __launch_bounds__(64) g2k_joint_wave_kernel(
     float c[kL2];
     float ade = 0.f, fde = 0.f;
     if (on && kind) {
-      joint_coords(kind, k, mu, tg, gs, e0, Nmax, seed_lo, seed_hi, c, ade, fde);
-      float4* dst = mine + i * 6;
-#pragma unroll
-      for (int r = 0; r < 6; ++r) dst[r] = make_float4(c[4 * r], c[4 * r + 1], c[4 * r + 2], c[4 * r + 3]);
+      joint_coords(head, kind, k, mu, tg, e0, Nmax, seed_lo, seed_hi, c, ade, fde);
+      joint_store(mine + i * 6, c);
     } else {
 #pragma unroll
       for (int r = 0; r < kL2; ++r) c[r] = 0.f;
@@ -344,7 +380,7 @@ __global__ void __launch_bounds__(64) g2k_joint_wave_kernel(
         const float xj[4] = {a.x, a.y, a.z, a.w}, yj[4] = {bq.x, bq.y, bq.z, bq.w};
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
-          const float dx = c[4 * u + v] - xj[v], dy = c[kL + 4 * u + v] - yj[v];
+          const float dx = c[2 * (4 * u + v)] - xj[v], dy = c[2 * (4 * u + v) + 1] - yj[v];
           m = fminf(m, fmaf(dx, dx, dy * dy));
         }
       }
@@ -431,6 +467,36 @@ __global__ void __launch_bounds__(64) g2k_joint_rows_kernel(
   }
 }
 
+template <class Head>
+int joint_eval_launch_as(const g2k_dims* d, const float* pred, const float* targets,
+                         const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                         const float* head_params, uint64_t seed, int K, float radius,
+                         float* per_frame_f, int32_t* per_frame_i, float* sums_f, int64_t* sums_i,
+                         int32_t* rows, hipStream_t st) {
+  const JointGeom g = joint_geom(*d, K);
+  const int64_t units = (int64_t)d->S * d->F * g.KD;
+  if (units > 0x7fffffff)
+    return set_err(G2K_EINVAL, "%sjoint_eval: %lld workgroups", Head::kPrefix, (long long)units);
+  const float r2 = radius * radius;
+  const int shared = (d->flags & G2K_STEP_TARGETS_SHARED) ? 1 : 0;
+  if (units > 0) {
+    if (g.waves == 1)
+      hipLaunchKernelGGL(joint_wave_kernel<Head>, dim3((unsigned)units), dim3(64), 0, st, pred, targets,
+                         n_active, n_frames, ped_mask, head_params, d->F, d->Nmax, g.KD, K,
+                         (uint32_t)seed, (uint32_t)(seed >> 32), shared, r2, rows);
+    else
+      hipLaunchKernelGGL(joint_kernel<Head>, dim3((unsigned)units), dim3(kJtWaves * 64), 0, st, pred,
+                         targets, n_active, n_frames, ped_mask, head_params, d->F, d->Nmax, g.KD, K,
+                         (uint32_t)seed, (uint32_t)(seed >> 32), shared, r2, rows);
+    const int rc = check_launch("joint_kernel");
+    if (rc) return rc;
+  }
+  // the merge of the units' rows (KD per scene-frame): the same for every head
+  hipLaunchKernelGGL(g2k_joint_rows_kernel, dim3((unsigned)d->S), dim3(64), 0, st, rows, d->F, g.KD, K,
+                     per_frame_f, per_frame_i, sums_f, reinterpret_cast<long long*>(sums_i));
+  return check_launch("g2k_joint_rows_kernel");
+}
+
 }  // namespace
 
 // one row [10] per unit; at most joint_kd_max units per scene-frame
@@ -438,37 +504,14 @@ int64_t joint_eval_ws_bytes(const g2k_dims* d) {
   return (int64_t)d->S * (d->F > 1 ? d->F : 1) * joint_kd_max(*d) * kJtRow * 4;
 }
 
-int joint_eval_launch(const g2k_dims* d, const float* pred, const float* targets,
+int joint_eval_launch(bool fullcov, const g2k_dims* d, const float* pred, const float* targets,
                       const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
                       const float* head, uint64_t seed, int K, float radius, float* per_frame_f,
                       int32_t* per_frame_i, float* sums_f, int64_t* sums_i, int32_t* rows,
                       hipStream_t st) {
-  const JointGeom g = joint_geom(*d, K);
-  const int64_t units = (int64_t)d->S * d->F * g.KD;
-  if (units > 0x7fffffff) return set_err(G2K_EINVAL, "joint_eval: %lld workgroups", (long long)units);
-  const float r2 = radius * radius;
-  const int shared = (d->flags & G2K_STEP_TARGETS_SHARED) ? 1 : 0;
-  if (units > 0) {
-    if (g.waves == 1)
-      hipLaunchKernelGGL(g2k_joint_wave_kernel, dim3((unsigned)units), dim3(64), 0, st, pred, targets,
-                         n_active, n_frames, ped_mask, head, d->F, d->Nmax, g.KD, K, (uint32_t)seed,
-                         (uint32_t)(seed >> 32), shared, r2, rows);
-    else
-      hipLaunchKernelGGL(g2k_joint_kernel, dim3((unsigned)units), dim3(kJtWaves * 64), 0, st, pred, targets,
-                         n_active, n_frames, ped_mask, head, d->F, d->Nmax, g.KD, K, (uint32_t)seed,
-                         (uint32_t)(seed >> 32), shared, r2, rows);
-    const int rc = check_launch("g2k_joint_kernel");
-    if (rc) return rc;
-  }
-  return joint_rows_launch(d, rows, g.KD, K, per_frame_f, per_frame_i, sums_f, sums_i, st);
-}
-
-// the merge of the units' rows (KD per scene-frame): the same for every head
-int joint_rows_launch(const g2k_dims* d, const int32_t* rows, int KD, int K, float* per_frame_f,
-                      int32_t* per_frame_i, float* sums_f, int64_t* sums_i, hipStream_t st) {
-  hipLaunchKernelGGL(g2k_joint_rows_kernel, dim3((unsigned)d->S), dim3(64), 0, st, rows, d->F, KD, K,
-                     per_frame_f, per_frame_i, sums_f, reinterpret_cast<long long*>(sums_i));
-  return check_launch("g2k_joint_rows_kernel");
+  return (fullcov ? joint_eval_launch_as<FullCovHead> : joint_eval_launch_as<PerStepHead>)(
+      d, pred, targets, n_active, n_frames, ped_mask, head, seed, K, radius, per_frame_f, per_frame_i,
+      sums_f, sums_i, rows, st);
 }
 
 }  // namespace g2k

@@ -41,7 +41,7 @@ trajectory and not 12 independent steps) and reports its minADE_K / minFDE_K,
 joint NLL per pair, the share of trajectories inside its 90 % region, sum q /
 24 n and the mean correlation of the x-residuals at adjacent steps: how far
 from independent the steps are.  With --collision_radius R > 0 as well, one
-g2k_fullcov_joint_eval_f32 launch (csrc/g2k_fullcov_joint.hip) follows: the
+g2k_fullcov_joint_eval_f32 launch (csrc/g2k_joint.hip) follows: the
 same K correlated draws taken as joint samples (FULLCOV_JOINT_FIGURES: JADE_K,
 JFDE_K, the collision rate of the samples and of each scene's best joint
 sample), logged next to the per-step head's.  The units caveat above holds for a pooled fit too: eth_hotel

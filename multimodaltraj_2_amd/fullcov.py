@@ -13,7 +13,7 @@ second moments, the joint NLL, the innovations q_t and their coverage),
 draws one reproducible trajectory per (scene, frame, pedestrian),
 ``best_of_k`` evaluates K such draws against the targets in one launch and
 ``joint_eval`` takes them as joint samples of a scene-frame (JADE_K / JFDE_K
-and the collision counts, csrc/g2k_fullcov_joint.hip), also in one launch."""
+and the collision counts, csrc/g2k_joint.hip), also in one launch."""
 from __future__ import annotations
 
 import ctypes
@@ -25,7 +25,7 @@ import torch
 
 from . import _lib
 from .frame_step import OBS_LEN, PRED_LEN, _check_dev, _ptr, _stream
-from .nll import DEFAULT_LEVELS, MAX_LEVELS, BestOfK, JointEval
+from .nll import DEFAULT_LEVELS, MAX_LEVELS, _best_of_k, _check_pairs_inputs, _joint_eval
 
 DIM = 2 * PRED_LEN
 
@@ -197,28 +197,6 @@ class FullCovHead:
             raise ValueError(f"chol must be [{DIM}, {DIM}]")
         _check_dev("chol", self.chol, dev, torch.float32)
 
-    def _check_inputs(self, d, pred, targets, n_active, n_frames, ped_mask, targets_shared):
-        dev = pred.device
-        S, F, Nmax = d.S, d.F, d.Nmax
-        if targets_shared:
-            d.flags = _lib.STEP_TARGETS_SHARED
-        _check_dev("pred", pred, dev, torch.float32)
-        if tuple(n_active.shape) != (S,):
-            raise ValueError("n_active must be [S]")
-        _check_dev("n_active", n_active, dev, torch.int32)
-        tshape = (S, 1 if targets_shared else F, Nmax, PRED_LEN, 2)
-        if tuple(targets.shape) != tshape:
-            raise ValueError(f"targets must be {list(tshape)}")
-        _check_dev("targets", targets, dev, torch.float32)
-        if n_frames is not None:
-            if tuple(n_frames.shape) != (S,):
-                raise ValueError("n_frames must be [S]")
-            _check_dev("n_frames", n_frames, dev, torch.int32)
-        if ped_mask is not None:
-            if tuple(ped_mask.shape) != (S, Nmax):
-                raise ValueError("ped_mask must be [S, Nmax]")
-            _check_dev("ped_mask", ped_mask, dev, torch.uint8)
-
     def _r2(self, levels, dev):
         """[2, NL] float64 on ``dev``: the levels' chi^2(2) radii (a step's
         innovation) and chi^2(24) radii (the whole trajectory); formed on the
@@ -248,7 +226,7 @@ class FullCovHead:
         lib = _lib.load()
         dev = pred.device
         d = self._dims(pred)
-        self._check_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
+        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
         if use_head:
             self._check_chol(dev)
         nl = len(levels)
@@ -301,27 +279,11 @@ class FullCovHead:
         """Best-of-K in one launch (g2k_fullcov_best_of_k_f32): of the K draws
         ``sample(pred, seed + i)``, i < k, each pair's smallest ADE and FDE and
         the draws that attain them -> nll.BestOfK."""
-        lib = _lib.load()
-        dev = pred.device
         d = self._dims(pred)
-        self._check_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
-        self._check_chol(dev)
-        k = int(k)
-        if not 1 <= k <= 4096:
-            raise ValueError(f"k = {k}: 1..4096")
-        S, F, Nmax = d.S, d.F, d.Nmax
-        sums = torch.empty((S, 8), dtype=torch.float32, device=dev)
-        per_ped = torch.empty((S, F, Nmax, 4), dtype=torch.float32, device=dev) if want_per_ped else None
-        best = torch.empty_like(pred) if want_best else None
-        ws = torch.empty(max(1, int(lib.g2k_fullcov_best_of_k_workspace_bytes(ctypes.byref(d)))),
-                         dtype=torch.uint8, device=dev)
-        rc = lib.g2k_fullcov_best_of_k_f32(ctypes.byref(d), _ptr(pred), _ptr(targets), _ptr(n_active),
-                                           _ptr(n_frames), _ptr(ped_mask), _ptr(self.chol),
-                                           ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), k,
-                                           _ptr(per_ped), _ptr(best), _ptr(sums), _ptr(ws),
-                                           ws.numel(), _stream(stream))
-        _lib.check("g2k_fullcov_best_of_k_f32", rc)
-        return BestOfK(sums=sums, per_ped=per_ped, best=best)
+        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
+        self._check_chol(pred.device)
+        return _best_of_k("g2k_fullcov_best_of_k_f32", self.chol, d, pred, targets, n_active, k, seed,
+                          n_frames, ped_mask, want_per_ped, want_best, stream)
 
     def joint_eval(self, pred, targets, n_active, k, radius, seed=0, *, n_frames=None, ped_mask=None,
                    targets_shared=False, want_per_frame=True, stream=None):
@@ -332,31 +294,8 @@ class FullCovHead:
         any of the 12 predicted steps, in the draws, the mean prediction and the
         targets -> nll.JointEval (GaussianHead.joint_eval with this head's
         correlated draws)."""
-        lib = _lib.load()
-        dev = pred.device
         d = self._dims(pred)
-        self._check_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
-        self._check_chol(dev)
-        k = int(k)
-        if not 1 <= k <= 4096:
-            raise ValueError(f"k = {k}: 1..4096")
-        radius = float(radius)
-        if not (math.isfinite(radius) and radius >= 0.0):
-            raise ValueError(f"radius = {radius}: finite and >= 0")
-        if dev.type != "cuda":
-            raise ValueError(f"pred: on {dev}, expected a GPU tensor")
-        S, F = d.S, d.F
-        sums_f = torch.empty((S, 4), dtype=torch.float32, device=dev)
-        sums_i = torch.empty((S, 6), dtype=torch.int64, device=dev)
-        pf = torch.empty((S, F, 4), dtype=torch.float32, device=dev) if want_per_frame else None
-        pi = torch.empty((S, F, 6), dtype=torch.int32, device=dev) if want_per_frame else None
-        ws = torch.empty(max(1, int(lib.g2k_fullcov_joint_eval_workspace_bytes(ctypes.byref(d)))),
-                         dtype=torch.uint8, device=dev)
-        rc = lib.g2k_fullcov_joint_eval_f32(ctypes.byref(d), _ptr(pred), _ptr(targets), _ptr(n_active),
-                                            _ptr(n_frames), _ptr(ped_mask), _ptr(self.chol),
-                                            ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), k,
-                                            ctypes.c_float(radius), _ptr(pf), _ptr(pi), _ptr(sums_f),
-                                            _ptr(sums_i), _ptr(ws), ws.numel(), _stream(stream))
-        _lib.check("g2k_fullcov_joint_eval_f32", rc)
-        return JointEval(sums_f=sums_f, sums_i=sums_i, per_frame_f=pf, per_frame_i=pi, k=k,
-                         radius=radius)
+        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
+        self._check_chol(pred.device)
+        return _joint_eval("g2k_fullcov_joint_eval_f32", self.chol, d, pred, targets, n_active, k,
+                           radius, seed, n_frames, ped_mask, want_per_frame, stream, gpu_only=True)

@@ -18,6 +18,7 @@ closed-form maximum-likelihood one of the residuals (csrc/g2k_calib.hip)."""
 from __future__ import annotations
 
 import ctypes
+import math
 from dataclasses import dataclass
 
 import numpy as np
@@ -213,6 +214,89 @@ MAX_LEVELS = 32
 DEFAULT_LEVELS = (0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9, 0.95, 0.99)
 
 
+def _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared):
+    """What every evaluation over the pairs takes, whatever the head: pred,
+    targets ([S, 1, ...] when shared: sets the flag in ``d``), n_active and
+    the optional n_frames / ped_mask, all on pred's device."""
+    dev = pred.device
+    S, F, Nmax = d.S, d.F, d.Nmax
+    if targets_shared:
+        d.flags = _lib.STEP_TARGETS_SHARED
+    _check_dev("pred", pred, dev, torch.float32)
+    if tuple(n_active.shape) != (S,):
+        raise ValueError("n_active must be [S]")
+    _check_dev("n_active", n_active, dev, torch.int32)
+    tshape = (S, 1 if targets_shared else F, Nmax, PRED_LEN, 2)
+    if tuple(targets.shape) != tshape:
+        raise ValueError(f"targets must be {list(tshape)}")
+    _check_dev("targets", targets, dev, torch.float32)
+    if n_frames is not None:
+        if tuple(n_frames.shape) != (S,):
+            raise ValueError("n_frames must be [S]")
+        _check_dev("n_frames", n_frames, dev, torch.int32)
+    if ped_mask is not None:
+        if tuple(ped_mask.shape) != (S, Nmax):
+            raise ValueError("ped_mask must be [S, Nmax]")
+        _check_dev("ped_mask", ped_mask, dev, torch.uint8)
+
+
+def _best_of_k(symbol, head, d, pred, targets, n_active, k, seed, n_frames, ped_mask, want_per_ped,
+               want_best, stream):
+    """The marginal best-of-K entry point ``symbol`` (g2k_best_of_k_f32 or
+    g2k_fullcov_best_of_k_f32) on checked inputs; ``head`` is that head's
+    parameter tensor -> BestOfK."""
+    lib = _lib.load()
+    dev = pred.device
+    k = int(k)
+    if not 1 <= k <= 4096:
+        raise ValueError(f"k = {k}: 1..4096")
+    S, F, Nmax = d.S, d.F, d.Nmax
+    sums = torch.empty((S, 8), dtype=torch.float32, device=dev)
+    per_ped = torch.empty((S, F, Nmax, 4), dtype=torch.float32, device=dev) if want_per_ped else None
+    best = torch.empty_like(pred) if want_best else None
+    size = getattr(lib, symbol.replace("_f32", "_workspace_bytes"))
+    ws = torch.empty(max(1, int(size(ctypes.byref(d)))), dtype=torch.uint8, device=dev)
+    rc = getattr(lib, symbol)(ctypes.byref(d), _ptr(pred), _ptr(targets), _ptr(n_active),
+                              _ptr(n_frames), _ptr(ped_mask), _ptr(head),
+                              ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), k, _ptr(per_ped), _ptr(best),
+                              _ptr(sums), _ptr(ws), ws.numel(), _stream(stream))
+    _lib.check(symbol, rc)
+    return BestOfK(sums=sums, per_ped=per_ped, best=best)
+
+
+def _joint_eval(symbol, head, d, pred, targets, n_active, k, radius, seed, n_frames, ped_mask,
+                want_per_frame, stream, gpu_only=False):
+    """The joint best-of-K entry point ``symbol`` (g2k_joint_eval_f32 or
+    g2k_fullcov_joint_eval_f32) on checked inputs; ``head`` is that head's
+    parameter tensor -> JointEval.  ``gpu_only``: the full-covariance head's
+    wrapper also refuses host tensors (_check_dev only compares devices)."""
+    lib = _lib.load()
+    dev = pred.device
+    k = int(k)
+    if not 1 <= k <= 4096:
+        raise ValueError(f"k = {k}: 1..4096")
+    radius = float(radius)
+    if not (math.isfinite(radius) and radius >= 0.0):
+        raise ValueError(f"radius = {radius}: finite and >= 0")
+    if gpu_only and dev.type != "cuda":
+        raise ValueError(f"pred: on {dev}, expected a GPU tensor")
+    S, F = d.S, d.F
+    sums_f = torch.empty((S, 4), dtype=torch.float32, device=dev)
+    sums_i = torch.empty((S, 6), dtype=torch.int64, device=dev)
+    pf = torch.empty((S, F, 4), dtype=torch.float32, device=dev) if want_per_frame else None
+    pi = torch.empty((S, F, 6), dtype=torch.int32, device=dev) if want_per_frame else None
+    size = getattr(lib, symbol.replace("_f32", "_workspace_bytes"))
+    ws = torch.empty(max(1, int(size(ctypes.byref(d)))), dtype=torch.uint8, device=dev)
+    rc = getattr(lib, symbol)(ctypes.byref(d), _ptr(pred), _ptr(targets), _ptr(n_active),
+                              _ptr(n_frames), _ptr(ped_mask), _ptr(head),
+                              ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), k, ctypes.c_float(radius),
+                              _ptr(pf), _ptr(pi), _ptr(sums_f), _ptr(sums_i), _ptr(ws), ws.numel(),
+                              _stream(stream))
+    _lib.check(symbol, rc)
+    return JointEval(sums_f=sums_f, sums_i=sums_i, per_frame_f=pf, per_frame_i=pi, k=k,
+                     radius=radius)
+
+
 class GaussianHead:
     def __init__(self, log_sigma=0.0, device="cuda"):
         h = torch.zeros((3, PRED_LEN), dtype=torch.float32, device=device)
@@ -253,43 +337,11 @@ class GaussianHead:
         """Best-of-K sampling evaluation in one launch (g2k_best_of_k_f32): of
         the K draws ``sample(pred, seed + i)``, i < k, each pair's smallest ADE
         and FDE and the draws that attain them -> BestOfK."""
-        lib = _lib.load()
-        dev = pred.device
         d = self._dims(pred)
-        S, F, Nmax = d.S, d.F, d.Nmax
-        if targets_shared:
-            d.flags = _lib.STEP_TARGETS_SHARED
-        _check_dev("pred", pred, dev, torch.float32)
-        _check_dev("head", self.head, dev, torch.float32)
-        if tuple(n_active.shape) != (S,):
-            raise ValueError("n_active must be [S]")
-        _check_dev("n_active", n_active, dev, torch.int32)
-        tshape = (S, 1 if targets_shared else F, Nmax, PRED_LEN, 2)
-        if tuple(targets.shape) != tshape:
-            raise ValueError(f"targets must be {list(tshape)}")
-        _check_dev("targets", targets, dev, torch.float32)
-        if n_frames is not None:
-            if tuple(n_frames.shape) != (S,):
-                raise ValueError("n_frames must be [S]")
-            _check_dev("n_frames", n_frames, dev, torch.int32)
-        if ped_mask is not None:
-            if tuple(ped_mask.shape) != (S, Nmax):
-                raise ValueError("ped_mask must be [S, Nmax]")
-            _check_dev("ped_mask", ped_mask, dev, torch.uint8)
-        k = int(k)
-        if not 1 <= k <= 4096:
-            raise ValueError(f"k = {k}: 1..4096")
-        sums = torch.empty((S, 8), dtype=torch.float32, device=dev)
-        per_ped = torch.empty((S, F, Nmax, 4), dtype=torch.float32, device=dev) if want_per_ped else None
-        best = torch.empty_like(pred) if want_best else None
-        ws = torch.empty(max(1, int(lib.g2k_best_of_k_workspace_bytes(ctypes.byref(d)))),
-                         dtype=torch.uint8, device=dev)
-        rc = lib.g2k_best_of_k_f32(ctypes.byref(d), _ptr(pred), _ptr(targets), _ptr(n_active),
-                                   _ptr(n_frames), _ptr(ped_mask), _ptr(self.head),
-                                   ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), k, _ptr(per_ped),
-                                   _ptr(best), _ptr(sums), _ptr(ws), ws.numel(), _stream(stream))
-        _lib.check("g2k_best_of_k_f32", rc)
-        return BestOfK(sums=sums, per_ped=per_ped, best=best)
+        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
+        _check_dev("head", self.head, pred.device, torch.float32)
+        return _best_of_k("g2k_best_of_k_f32", self.head, d, pred, targets, n_active, k, seed,
+                          n_frames, ped_mask, want_per_ped, want_best, stream)
 
     def joint_eval(self, pred, targets, n_active, k, radius, seed=0, *, n_frames=None, ped_mask=None,
                    targets_shared=False, want_per_frame=True, stream=None):
@@ -299,50 +351,11 @@ class GaussianHead:
         JFDE_K) and the couples that come closer than ``radius`` at any of the
         12 predicted steps, in the draws, the mean prediction and the targets
         -> JointEval."""
-        import math
-        lib = _lib.load()
-        dev = pred.device
         d = self._dims(pred)
-        S, F, Nmax = d.S, d.F, d.Nmax
-        if targets_shared:
-            d.flags = _lib.STEP_TARGETS_SHARED
-        _check_dev("pred", pred, dev, torch.float32)
-        _check_dev("head", self.head, dev, torch.float32)
-        if tuple(n_active.shape) != (S,):
-            raise ValueError("n_active must be [S]")
-        _check_dev("n_active", n_active, dev, torch.int32)
-        tshape = (S, 1 if targets_shared else F, Nmax, PRED_LEN, 2)
-        if tuple(targets.shape) != tshape:
-            raise ValueError(f"targets must be {list(tshape)}")
-        _check_dev("targets", targets, dev, torch.float32)
-        if n_frames is not None:
-            if tuple(n_frames.shape) != (S,):
-                raise ValueError("n_frames must be [S]")
-            _check_dev("n_frames", n_frames, dev, torch.int32)
-        if ped_mask is not None:
-            if tuple(ped_mask.shape) != (S, Nmax):
-                raise ValueError("ped_mask must be [S, Nmax]")
-            _check_dev("ped_mask", ped_mask, dev, torch.uint8)
-        k = int(k)
-        if not 1 <= k <= 4096:
-            raise ValueError(f"k = {k}: 1..4096")
-        radius = float(radius)
-        if not (math.isfinite(radius) and radius >= 0.0):
-            raise ValueError(f"radius = {radius}: finite and >= 0")
-        sums_f = torch.empty((S, 4), dtype=torch.float32, device=dev)
-        sums_i = torch.empty((S, 6), dtype=torch.int64, device=dev)
-        pf = torch.empty((S, F, 4), dtype=torch.float32, device=dev) if want_per_frame else None
-        pi = torch.empty((S, F, 6), dtype=torch.int32, device=dev) if want_per_frame else None
-        ws = torch.empty(max(1, int(lib.g2k_joint_eval_workspace_bytes(ctypes.byref(d)))),
-                         dtype=torch.uint8, device=dev)
-        rc = lib.g2k_joint_eval_f32(ctypes.byref(d), _ptr(pred), _ptr(targets), _ptr(n_active),
-                                    _ptr(n_frames), _ptr(ped_mask), _ptr(self.head),
-                                    ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), k,
-                                    ctypes.c_float(radius), _ptr(pf), _ptr(pi), _ptr(sums_f),
-                                    _ptr(sums_i), _ptr(ws), ws.numel(), _stream(stream))
-        _lib.check("g2k_joint_eval_f32", rc)
-        return JointEval(sums_f=sums_f, sums_i=sums_i, per_frame_f=pf, per_frame_i=pi, k=k,
-                         radius=radius)
+        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
+        _check_dev("head", self.head, pred.device, torch.float32)
+        return _joint_eval("g2k_joint_eval_f32", self.head, d, pred, targets, n_active, k, radius,
+                           seed, n_frames, ped_mask, want_per_frame, stream)
 
     def _r2(self, levels, dev):
         """The levels' radii -2 log1p(-p), float64, on ``dev`` (formed on the
@@ -370,27 +383,10 @@ class GaussianHead:
         lib = _lib.load()
         dev = pred.device
         d = self._dims(pred)
-        S, F, Nmax = d.S, d.F, d.Nmax
-        if targets_shared:
-            d.flags = _lib.STEP_TARGETS_SHARED
-        _check_dev("pred", pred, dev, torch.float32)
+        S = d.S
+        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
         if use_head:
             _check_dev("head", self.head, dev, torch.float32)
-        if tuple(n_active.shape) != (S,):
-            raise ValueError("n_active must be [S]")
-        _check_dev("n_active", n_active, dev, torch.int32)
-        tshape = (S, 1 if targets_shared else F, Nmax, PRED_LEN, 2)
-        if tuple(targets.shape) != tshape:
-            raise ValueError(f"targets must be {list(tshape)}")
-        _check_dev("targets", targets, dev, torch.float32)
-        if n_frames is not None:
-            if tuple(n_frames.shape) != (S,):
-                raise ValueError("n_frames must be [S]")
-            _check_dev("n_frames", n_frames, dev, torch.int32)
-        if ped_mask is not None:
-            if tuple(ped_mask.shape) != (S, Nmax):
-                raise ValueError("ped_mask must be [S, Nmax]")
-            _check_dev("ped_mask", ped_mask, dev, torch.uint8)
         nl = len(levels)
         r2 = self._r2(levels, dev) if nl else None
         # S = 0 launches nothing: the outputs are the empty launch's zeros

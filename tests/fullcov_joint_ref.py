@@ -1,5 +1,5 @@
 """float64 checker of the joint best-of-K evaluation of the full-covariance
-head (g2k_fullcov_joint_eval_f32; csrc/g2k_fullcov_joint.hip states the
+head (g2k_fullcov_joint_eval_f32; csrc/g2k_joint.hip states the
 definition): tests/joint_ref.joint_eval_ref with one change — joint sample k is
 tests/fullcov_ref.sample at seed (seed + k) mod 2^64 and factor ``chol``.  Built
 from the parts of the existing checkers (draw_errors, pair_mask, min_dist,

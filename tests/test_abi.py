@@ -302,3 +302,205 @@ def test_loop_invariant_launches_hold_one_ring_slot():
     assert lds(29, True, 2) == lds(29, False, 2)                     # split: general path
     assert lds(20, True, 1, stride=1, W=27) == lds(20, False, 1, stride=1, W=27)
     assert fs.step_coresidency(128, 29, 128, 32, 8, 0, True, True) == 2
+
+
+# ---------------------------------------------------------------------------
+# the probabilistic heads' entry points: every rejection, its status code and
+# a distinguishing word of its message; the workspace sizes
+# ---------------------------------------------------------------------------
+_P = 16                        # a non-NULL pointer, 16-byte aligned (never dereferenced)
+_EINVAL, _EUNSUPPORTED = -1, -4
+
+
+def _err(lib):
+    return lib.g2k_last_error() or b""
+
+
+class _Call:
+    """One entry point with named arguments that default to a valid call;
+    ``rc(dims, name=value, ...)`` calls it with some replaced (``dims=None``:
+    a NULL dims pointer)."""
+
+    def __init__(self, lib, fn, order, **defaults):
+        self.lib, self.fn, self.order, self.defaults = lib, getattr(lib, fn), order, defaults
+
+    def rc(self, d, **kw):
+        a = dict(self.defaults)
+        assert set(kw) <= set(a), kw
+        a.update(kw)
+        return self.fn(ctypes.byref(d) if d is not None else None, *[a[n] for n in self.order])
+
+    def rejects(self, code, word, d, **kw):
+        rc = self.rc(d, **kw)
+        msg = _err(self.lib)
+        assert rc == code and word in msg, (self.fn.__name__, kw, rc, msg)
+
+
+_MARGINAL = ("pred", "targets", "n_active", "n_frames", "ped_mask", "head", "seed", "K", "per_ped",
+             "best", "out", "ws", "ws_bytes", "stream")
+_JOINT = ("pred", "targets", "n_active", "n_frames", "ped_mask", "head", "seed", "K", "radius",
+          "per_frame_f", "per_frame_i", "sums_f", "sums_i", "ws", "ws_bytes", "stream")
+
+
+@pytest.mark.parametrize("fn,short,joint", [
+    ("g2k_best_of_k_f32", b"best_of_k", False),
+    ("g2k_fullcov_best_of_k_f32", b"fullcov_best_of_k", False),
+    ("g2k_joint_eval_f32", b"joint_eval", True),
+    ("g2k_fullcov_joint_eval_f32", b"fullcov_joint_eval", True)])
+def test_sampled_evaluation_entry_points_validate(fn, short, joint):
+    lib = _lib.load()
+    d = _dims()
+    need = getattr(lib, fn.replace("_f32", "_workspace_bytes"))(ctypes.byref(d))
+    assert need > 0
+    common = dict(pred=_P, targets=_P, n_active=_P, n_frames=None, ped_mask=None, head=_P, seed=7,
+                  K=20, ws=_P, ws_bytes=need, stream=None)
+    if joint:
+        c = _Call(lib, fn, _JOINT, radius=0.1, per_frame_f=None, per_frame_i=None, sums_f=_P,
+                  sums_i=_P, **common)
+        required = ("pred", "targets", "n_active", "head", "sums_f", "sums_i")
+    else:
+        c = _Call(lib, fn, _MARGINAL, per_ped=_P, best=None, out=_P, **common)
+        required = ("pred", "targets", "n_active", "head", "out")
+    c.rejects(_EINVAL, b"dims is NULL", None)
+    c.rejects(_EUNSUPPORTED, short + b" reads pred_path_band", _dims(flags=_lib.STEP_PRED_PED_MAJOR))
+    assert _err(lib).startswith(short)
+    c.rejects(_EINVAL, b"Nmax=0", _dims(Nmax=0))
+    c.rejects(_EINVAL, b"Nmax=257", _dims(Nmax=257))
+    c.rejects(_EINVAL, b"S=-1", _dims(S=-1))
+    c.rejects(_EINVAL, b"F=-1", _dims(F=-1))
+    c.rejects(_EINVAL, b"K=0 ", d, K=0)
+    c.rejects(_EINVAL, b"K=4097 ", d, K=4097)
+    if joint:
+        for r in (-1.0, float("nan"), float("inf")):
+            c.rejects(_EINVAL, b"radius=", d, radius=r)
+        c.rejects(_EINVAL, b"K=0 ", d, K=0, radius=-1.0)           # K before the radius
+        c.rejects(_EINVAL, b"radius=", d, radius=-1.0, pred=None)   # the radius before the pointers
+    for name in required:
+        c.rejects(_EINVAL, b"required buffer pointer is NULL", d, **{name: None})
+    c.rejects(_EINVAL, b"required buffer", d, pred=None, targets=20)   # NULLs before alignment
+    c.rejects(_EINVAL, b"targets must be 8-byte aligned", d, targets=20)
+    if joint:
+        c.rejects(_EINVAL, b"sums_i must be 8-byte aligned", d, sums_i=20)
+        c.rejects(_EINVAL, b"targets", d, targets=20, sums_i=20)
+        c.rejects(_EINVAL, b"sums_i", d, sums_i=20, ws=None)        # alignment before the workspace
+        c.rejects(_EINVAL, b"4-byte aligned", d, ws=18)
+        assert c.rc(_dims(S=0), ws=18, ws_bytes=0) == 0            # ... looked at only when S > 0
+    else:
+        c.rejects(_EINVAL, b"per_ped must be 16-byte aligned", d, per_ped=24)
+        c.rejects(_EINVAL, b"targets", d, targets=20, per_ped=24)
+        c.rejects(_EINVAL, b"per_ped", d, per_ped=24, ws=None)
+    c.rejects(_EINVAL, b"workspace of %d bytes needed (got %d)" % (need, need), d, ws=None)
+    assert joint or _err(lib).endswith(b"(got %d)" % need)        # the marginal pair asks no alignment
+    c.rejects(_EINVAL, b"workspace of %d bytes needed (got %d)" % (need, need - 4), d,
+              ws_bytes=need - 4)
+    # no scene: nothing to do, and no workspace needed; T and L are not looked at
+    assert c.rc(_dims(S=0), ws=None, ws_bytes=0) == 0
+    assert c.rc(_dims(S=0, T=9, L=10, D=3, H=5), ws=None, ws_bytes=0) == 0
+    c.rejects(_EINVAL, b"K=0 ", _dims(S=0), K=0)                   # S = 0 is still validated
+    c.rejects(_EINVAL, b"required buffer", _dims(S=0), head=None)
+
+
+_STATS = ("pred", "targets", "n_active", "n_frames", "ped_mask", "head", "r2", "n_levels")
+
+
+@pytest.mark.parametrize("fn,short,head,outs", [
+    ("g2k_head_stats_f32", b"head_stats", b"head", ("stats",)),
+    ("g2k_fullcov_stats_f32", b"fullcov_stats", b"chol", ("moments", "stats"))])
+def test_stats_entry_points_validate(fn, short, head, outs):
+    lib = _lib.load()
+    size = getattr(lib, fn.replace("_f32", "_workspace_bytes"))
+    d = _dims()                                                   # 1280 slots: more than one workgroup
+    need = size(ctypes.byref(d), 4)
+    assert need > 0 and size(ctypes.byref(_dims(S=1, F=1)), 4) == 0
+    order = _STATS + outs + ("inside", "fit", "ws", "ws_bytes", "stream")
+    c = _Call(lib, fn, order, pred=_P, targets=_P, n_active=_P, n_frames=None, ped_mask=None,
+              head=_P, r2=_P, n_levels=4, inside=_P, fit=_P, ws=_P, ws_bytes=need, stream=None,
+              **{o: _P for o in outs})
+    c.rejects(_EINVAL, b"dims is NULL", None)
+    c.rejects(_EUNSUPPORTED, short + b" reads pred_path_band", _dims(flags=_lib.STEP_PRED_PED_MAJOR))
+    assert _err(lib).startswith(short)
+    for bad in (dict(Nmax=0), dict(Nmax=257), dict(S=-1), dict(F=-1), dict(S=1 << 16, F=1 << 15)):
+        c.rejects(_EINVAL, b"n_levels 0..32, S F < 2^31", _dims(**bad))
+        assert size(ctypes.byref(_dims(**bad)), 4) == -1
+    c.rejects(_EINVAL, b"n_levels=-1 ", d, n_levels=-1)
+    c.rejects(_EINVAL, b"n_levels=33 ", d, n_levels=33)
+    assert size(ctypes.byref(d), -1) == -1 and size(ctypes.byref(d), 33) == -1 and size(None, 4) == -1
+    for name in ("pred", "targets", "n_active") + outs:
+        c.rejects(_EINVAL, b"required buffer pointer is NULL", d, **{name: None})
+    c.rejects(_EINVAL, head + b" is NULL: n_levels must be 0 and inside NULL", d, head=None)
+    c.rejects(_EINVAL, head + b" is NULL", d, head=None, n_levels=0, r2=None)       # inside given
+    c.rejects(_EINVAL, b"r2 is NULL with n_levels=4", d, r2=None)
+    c.rejects(_EINVAL, head + b" is NULL", d, head=None, r2=None)                    # head before r2
+    c.rejects(_EINVAL, b"targets must be 8-byte aligned", d, targets=20)
+    c.rejects(_EINVAL, b"r2 is NULL", d, r2=None, targets=20)                        # r2 before alignment
+    words = ", ".join(outs).encode() + b", inside and r2 must be 8-byte aligned"
+    for name in outs + ("inside", "r2"):
+        c.rejects(_EINVAL, words, d, **{name: 20})
+    c.rejects(_EINVAL, b"targets", d, targets=20, stats=20)
+    c.rejects(_EINVAL, b"workspace of %d bytes needed (got %d), 8-byte aligned" % (need, need), d,
+              ws=None)
+    c.rejects(_EINVAL, b"workspace of %d bytes needed (got %d), 8-byte aligned" % (need, need - 4), d,
+              ws_bytes=need - 4)
+    c.rejects(_EINVAL, b"8-byte aligned", d, ws=20)
+    c.rejects(_EINVAL, b"stats", d, stats=20, ws=None)                               # before the workspace
+    # one workgroup: no workspace; no scene: nothing to do; T and L are not looked at
+    assert c.rc(_dims(S=0), ws=None, ws_bytes=0) == 0
+    assert c.rc(_dims(S=0, T=9, L=10, D=3, H=5), ws=None, ws_bytes=0) == 0
+    assert c.rc(_dims(S=0), head=None, r2=None, n_levels=0, inside=None, fit=None, ws=None,
+                ws_bytes=0) == 0
+    c.rejects(_EINVAL, b"required buffer", _dims(S=0), stats=None)
+
+
+@pytest.mark.parametrize("fn", ["g2k_gauss_sample_f32", "g2k_fullcov_sample_f32"])
+def test_sampler_entry_points_validate(fn):
+    lib = _lib.load()
+    c = _Call(lib, fn, ("pred", "head", "seed", "out", "stream"), pred=_P, head=_P, seed=3, out=_P,
+              stream=None)
+    c.rejects(_EINVAL, b"dims is NULL", None)
+    c.rejects(_EUNSUPPORTED, b"flags must be 0", _dims(flags=_lib.STEP_PRED_PED_MAJOR))
+    c.rejects(_EUNSUPPORTED, b"flags must be 0", _dims(flags=_lib.STEP_TARGETS_SHARED))
+    c.rejects(_EUNSUPPORTED, b"T=9 L=12", _dims(T=9))
+    c.rejects(_EUNSUPPORTED, b"T=8 L=10", _dims(L=10))
+    c.rejects(_EINVAL, b"Nmax=0", _dims(Nmax=0))
+    c.rejects(_EINVAL, b"Nmax=257", _dims(Nmax=257))
+    c.rejects(_EINVAL, b"S=-1", _dims(S=-1))
+    c.rejects(_EINVAL, b"F=-1", _dims(F=-1))
+    c.rejects(_EINVAL, b"required buffer pointer is NULL", _dims(), pred=None)
+    c.rejects(_EINVAL, b"required buffer pointer is NULL", _dims(), head=None)
+    c.rejects(_EINVAL, b"out is NULL", _dims(), out=None)
+    c.rejects(_EINVAL, b"out is NULL", _dims(S=0), out=None)
+    assert c.rc(_dims(S=0)) == 0 and c.rc(_dims(F=0)) == 0
+
+
+def test_sampled_evaluation_workspace_sizes():
+    """The marginal evaluation keeps one row [8] of floats per (scene, frame)
+    at most, the joint one a row [10] of int32 per unit: joint_kd_max units per
+    scene-frame = as many as bring the launch to 2048 waves (Nmax <= 64) or 512
+    workgroups (Nmax > 64), 8 at most.  The two heads share both."""
+    lib = _lib.load()
+
+    def sizes(stem, **kw):
+        d = ctypes.byref(_dims(**kw))
+        a = getattr(lib, "g2k_%s_workspace_bytes" % stem)(d)
+        assert getattr(lib, "g2k_fullcov_%s_workspace_bytes" % stem)(d) == a, kw
+        return a
+
+    for S, F in [(2, 20), (1, 1), (3, 0), (0, 20), (256, 20), (7, 37)]:
+        assert sizes("best_of_k", S=S, F=F) == S * max(F, 1) * 32
+    # S F: far below the clamp, the last that still deals 8, the first that
+    # deals fewer (2048 / 8 = 256, then ceil(2048 / 293) = 7; 512 / 8 = 64,
+    # then ceil(512 / 74) = 7), the last that deals 2, one unit, no frame
+    for S, F in [(2, 20), (1, 1), (256, 1), (257, 1), (1, 293), (64, 1), (13, 5), (74, 1),
+                 (2047, 1), (2048, 1), (511, 1), (512, 1), (256, 20), (3, 0), (0, 20)]:
+        for Nmax, fill in [(32, 2048), (64, 2048), (65, 512), (256, 512)]:
+            sf = S * F
+            kd = min(8, -(-fill // sf)) if sf > 0 else 1
+            assert sizes("joint_eval", S=S, F=F, Nmax=Nmax) == S * max(F, 1) * kd * 40, (S, F, Nmax)
+    assert sizes("joint_eval", S=257, F=1, Nmax=32) == 257 * 8 * 40      # the clamp holds here
+    assert sizes("joint_eval", S=1, F=293, Nmax=32) == 293 * 7 * 40      # ... and not here
+    for stem in ("best_of_k", "joint_eval"):
+        for fn in ("g2k_%s_workspace_bytes" % stem, "g2k_fullcov_%s_workspace_bytes" % stem):
+            assert getattr(lib, fn)(None) == -1
+            assert getattr(lib, fn)(ctypes.byref(_dims(S=-1))) == -1
+            assert getattr(lib, fn)(ctypes.byref(_dims(F=-1))) == -1
+            assert getattr(lib, fn)(ctypes.byref(_dims(Nmax=0))) >= 0    # Nmax is not looked at

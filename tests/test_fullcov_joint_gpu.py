@@ -1,5 +1,5 @@
 """GPU: the fused joint best-of-K evaluation of the full-covariance head
-(g2k_fullcov_joint_eval_f32, csrc/g2k_fullcov_joint.hip; FullCovHead.joint_eval;
+(g2k_fullcov_joint_eval_f32, csrc/g2k_joint.hip; FullCovHead.joint_eval;
 evaluate.py --fullcov_head with --collision_radius) against the float64 checker
 tests/fullcov_joint_ref.py and against the device's own draws.  PARITY
 UNPINNED: the reference has no probabilistic head.
