@@ -646,6 +646,46 @@ int g2k_fullcov_joint_eval_f32(const g2k_dims* d, const float* pred, const float
                                float* sums_f, int64_t* sums_i, void* workspace,
                                int64_t workspace_bytes, void* stream);
 
+/*
+ * KDE-NLL of either head's samples (added after ABI 11; detect by symbol;
+ * csrc/g2k_kde.hip): the kernel-density likelihood of Trajectron++, two passes
+ * over the K draws, no draw in memory.  g2k_kde_nll_f32: inputs, pairs and draws
+ * as g2k_best_of_k_f32; g2k_fullcov_kde_nll_f32: as g2k_fullcov_best_of_k_f32
+ * (chol [24][24] in place of head).  G2K_STEP_TARGETS_SHARED is the only flag
+ * read; G2K_STEP_PRED_PED_MAJOR returns G2K_EUNSUPPORTED.  For a pair and a
+ * step t, x_k the K drawn positions, y the target:
+ *   c = sample covariance of the x_k (divisor K - 1), H = K^(-1/3) c (Scott's
+ *     factor K^(-1/(d+4)) squared, d = 2: scipy.stats.gaussian_kde's default)
+ *   logp_t = log(1/K sum_k exp(-1/2 (y - x_k)^T H^-1 (y - x_k))) - log 2 pi
+ *     - 1/2 log det H
+ *   term_t = max(logp_t, log_floor); a step is clipped when logp_t < log_floor
+ *     or det H is not a positive finite number (term_t = log_floor then)
+ *   kde_nll = -1/12 sum_t term_t, kde_nll_final = -term_11
+ *   (moments and distances in f32, the bandwidth in double)
+ *   per_ped [S, F, Nmax, 4] or NULL: {kde_nll, kde_nll_final, clipped steps,
+ *     0}, zeros for non-pairs (every element written; 16-byte aligned)
+ *   out [S, 8] = {sum kde_nll, sum kde_nll_final, pairs, sum clipped steps, K,
+ *     log_floor, 0, 0} over the scene's pairs, fixed order (every element
+ *     written)
+ * Nothing else is written but the workspace's first S max(F, 1) 32 bytes.
+ * K in 4..4096, log_floor finite, Nmax in 1..256, workspace >=
+ * g2k_kde_nll_workspace_bytes(d) = S max(F, 1) 32 (else G2K_EINVAL before any
+ * launch; -1 for a NULL d or a negative S or F); S = 0 or F = 0 is a no-op
+ * (nothing is launched or written).  Asynchronous, no allocation, capturable;
+ * no atomics: repeated calls are bit-identical.
+ */
+int64_t g2k_kde_nll_workspace_bytes(const g2k_dims* d);
+int g2k_kde_nll_f32(const g2k_dims* d, const float* pred, const float* targets,
+                    const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                    const float* head, uint64_t seed, int32_t K, float log_floor, float* per_ped,
+                    float* out, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t g2k_fullcov_kde_nll_workspace_bytes(const g2k_dims* d);
+int g2k_fullcov_kde_nll_f32(const g2k_dims* d, const float* pred, const float* targets,
+                            const int32_t* n_active, const int32_t* n_frames,
+                            const uint8_t* ped_mask, const float* chol, uint64_t seed, int32_t K,
+                            float log_floor, float* per_ped, float* out, void* workspace,
+                            int64_t workspace_bytes, void* stream);
+
 int64_t g2k_context_conv_workspace_bytes(int32_t Hh, int32_t Ww, int32_t D);
 int g2k_context_conv_f32(const float* img, int32_t Hh, int32_t Ww, int32_t C, const float* filt,
                          int32_t D, float lambda, float* out, float* G, void* workspace,

@@ -106,6 +106,13 @@ SYMBOLS = {
     "g2k_fullcov_joint_eval_f32": (c_int, [ctypes.POINTER(G2KDims), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                            ctypes.c_uint64, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp,
                                            c_i64, c_vp]),
+    "g2k_kde_nll_workspace_bytes": (c_i64, [ctypes.POINTER(G2KDims)]),
+    "g2k_kde_nll_f32": (c_int, [ctypes.POINTER(G2KDims), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                ctypes.c_uint64, c_i32, c_f32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "g2k_fullcov_kde_nll_workspace_bytes": (c_i64, [ctypes.POINTER(G2KDims)]),
+    "g2k_fullcov_kde_nll_f32": (c_int, [ctypes.POINTER(G2KDims), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                        ctypes.c_uint64, c_i32, c_f32, c_vp, c_vp, c_vp, c_i64,
+                                        c_vp]),
     "g2k_step_grad_update_f32": (c_int, [ctypes.POINTER(G2KDims), ctypes.POINTER(G2KWeights),
                                          c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp,
                                          c_vp, c_i64, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp]),

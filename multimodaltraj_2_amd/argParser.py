@@ -3,7 +3,7 @@ the build's own: --data_root (Q8), --device, --mode,
 --world_size, --n_max, --train_batch, --train_scenes, --valid_from_seed,
 --log_dir, --save_dir, --seed, --use_grid_lstm, --loss, --num_samples,
 --sample_seed, --head_log_sigma, --collision_radius, --fit_head,
---calibration, --fullcov_head."""
+--calibration, --fullcov_head, --kde_nll, --kde_floor."""
 import argparse
 
 
@@ -79,6 +79,14 @@ class ArgsParser:
                              'datasets (train; honours --train_scenes) or of the left-out dataset '
                              'itself (eval: in-sample, a bound), and report its minADE_K / minFDE_K, '
                              'joint NLL, coverage and the lag-1 correlation of the residuals')
+    parser.add_argument('--kde_nll', type=int, choices=(0, 1), default=0,
+                        help='--num_samples K (K >= 4): 1 also reports the KDE-NLL of the K draws '
+                             '(per step a Gaussian kernel density estimate of the drawn positions, '
+                             "Scott's bandwidth, and the target's negative log density under it), "
+                             'of the per-step head and, with --fullcov_head, of the '
+                             'full-covariance head')
+    parser.add_argument('--kde_floor', type=float, default=-20.0,
+                        help='--kde_nll: the floor of a step\'s log density')
     parser.add_argument('--train_scenes', type=int, default=0,
                         help='--mode train: distinct scenes used (0: all of the fold)')
     parser.add_argument('--valid_from_seed', type=int, default=0,

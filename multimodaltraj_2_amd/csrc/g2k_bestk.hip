@@ -36,7 +36,8 @@
 // c]), draws in registers and keeps its running minima; the KS lanes' minima
 // are combined by a butterfly on (value, index), lexicographic, so the lowest k
 // wins a tie whatever KS is.
-// KS and FC come from the shapes alone (bestk_geom): KS grows until the launch
+// KS and FC come from the shapes alone (bestk_geom, g2k_bestk_geom.h, shared
+// with g2k_kde.hip): KS grows until the launch
 // has ~2 * 256 CUs * 1024 items or K is used up, FC fills the 256 threads —
 // S 256 x F 20 x Nmax 32 runs KS 4, FC 2 (2560 workgroups), real-data
 // evaluation (F 1, n_active down to 2, K 20) runs KS 16 (a pair per quarter
@@ -45,31 +46,12 @@
 // Scene sums: per-workgroup rows [S * C][8] in the caller's workspace, then
 // g2k_bestk_rows_kernel adds a scene's C rows in chunk order (no atomics);
 // C == 1 writes out directly.
+#include "g2k_bestk_geom.h"
 #include "g2k_common.h"
 #include "g2k_head_draw.h"
 
 namespace g2k {
 namespace {
-
-constexpr int kBkThreads = 256;
-constexpr int64_t kBkFill = 2 * 256 * 1024;   // items that fill 256 CUs twice over
-constexpr int kBkMaxSlices = 64;              // one wave: the combine is lane shuffles
-
-struct BestkGeom { int ks_log2, FC, C; };
-
-BestkGeom bestk_geom(const g2k_dims& d, int K) {
-  const int64_t slots = (int64_t)d.S * d.F * d.Nmax;
-  int j = 0;
-  while ((2 << j) <= K && (2 << j) <= kBkMaxSlices && (slots << j) < kBkFill) ++j;
-  int fc = kBkThreads / (d.Nmax << j);
-  if (fc > d.F) fc = d.F;
-  if (fc < 1) fc = 1;
-  BestkGeom g;
-  g.ks_log2 = j;
-  g.FC = fc;
-  g.C = d.F > 0 ? (d.F + fc - 1) / fc : 1;
-  return g;
-}
 
 template <class Head>
 __global__ void __launch_bounds__(kBkThreads) best_of_k_kernel(

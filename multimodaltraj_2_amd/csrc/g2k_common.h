@@ -540,6 +540,13 @@ int joint_eval_launch(bool fullcov, const g2k_dims* d, const float* pred, const 
                       int32_t* per_frame_i, float* sums_f, int64_t* sums_i, int32_t* rows,
                       hipStream_t st);
 
+// g2k_kde.hip: the fused KDE-NLL of either head's samples (head as above)
+int64_t kde_nll_ws_bytes(const g2k_dims* d);
+int kde_nll_launch(bool fullcov, const g2k_dims* d, const float* pred, const float* targets,
+                   const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                   const float* head, uint64_t seed, int K, float log_floor, float* per_ped, float* out,
+                   float* rows, hipStream_t st);
+
 // g2k_calib.hip
 int64_t head_stats_ws_bytes(const g2k_dims* d, int n_levels);
 int head_stats_launch(const g2k_dims* d, const float* pred, const float* targets,

@@ -44,7 +44,15 @@ from independent the steps are.  With --collision_radius R > 0 as well, one
 g2k_fullcov_joint_eval_f32 launch (csrc/g2k_joint.hip) follows: the
 same K correlated draws taken as joint samples (FULLCOV_JOINT_FIGURES: JADE_K,
 JFDE_K, the collision rate of the samples and of each scene's best joint
-sample), logged next to the per-step head's.  The units caveat above holds for a pooled fit too: eth_hotel
+sample), logged next to the per-step head's.  --kde_nll 1 (K >= 4) adds the
+KDE-NLL of the same K draws, one g2k_kde_nll_f32 launch (csrc/g2k_kde.hip): per
+pedestrian and step a Gaussian kernel density estimate of the K drawn positions
+(Scott's bandwidth, scipy.stats.gaussian_kde's default) and the target's
+negative log density under it, floored at --kde_floor (KDE_FIGURES: the mean
+over the 12 steps, the last step's, and the share of steps on the floor) — the
+one likelihood figure with the same definition for both heads, so with
+--fullcov_head a g2k_fullcov_kde_nll_f32 launch adds FULLCOV_KDE_FIGURES; unlike
+minADE_K it grows when the head is too wide.  The units caveat above holds for a pooled fit too: eth_hotel
 is normalised, the UCY sets are world coordinates, so a fold that mixes them
 fits one width to both.  The build's: the reference has no probabilistic head
 (SURVEY.md §8(f) row 4), so these figures have no reference counterpart.
@@ -68,6 +76,8 @@ FULLCOV_FIGURES = ("fullcov_min_ade", "fullcov_min_fde", "fullcov_nll", "fullcov
                    "fullcov_q_ratio", "fullcov_lag1_corr")
 FULLCOV_JOINT_FIGURES = ("fullcov_jade", "fullcov_jfde", "fullcov_collision_rate",
                          "fullcov_collision_rate_best")
+KDE_FIGURES = ("kde_nll", "kde_nll_final", "kde_clipped")
+FULLCOV_KDE_FIGURES = tuple("fullcov_" + k for k in KDE_FIGURES)
 
 
 def calib_figures(hs):
@@ -93,6 +103,12 @@ def fullcov_joint_figures(je):
     JOINT_FIGURES)."""
     return dict(fullcov_jade=je.jade, fullcov_jfde=je.jfde, fullcov_collision_rate=je.collision_rate,
                 fullcov_collision_rate_best=je.collision_rate_best)
+
+
+def kde_figures(kd, prefix=""):
+    """KDE_FIGURES (``prefix`` "fullcov_": FULLCOV_KDE_FIGURES) of a KdeNll."""
+    return {prefix + "kde_nll": kd.kde_nll, prefix + "kde_nll_final": kd.kde_nll_final,
+            prefix + "kde_clipped": kd.clipped_share}
 
 
 def left_out_plan(args, nmax):
@@ -145,12 +161,18 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
     would, runs its stats and best_of_k on the left-out scenes and adds
     FULLCOV_FIGURES and a log line, and with --collision_radius R > 0 also
     FULLCOV_JOINT_FIGURES from one FullCovHead.joint_eval launch and one more
-    log line (``keep["fullcov"]["joint"]``).  ``keep`` (a dict)
+    log line (``keep["fullcov"]["joint"]``).  --kde_nll 1 adds KDE_FIGURES
+    from one GaussianHead.kde_nll launch (same K and seed, floor --kde_floor)
+    and a log line, and with --fullcov_head FULLCOV_KDE_FIGURES from one
+    FullCovHead.kde_nll launch and a log line (``keep["kde"]``,
+    ``keep["fullcov"]["kde"]``).  ``keep`` (a dict)
     receives the plan, the predictions, the head and the kernels' outputs for
     a caller that checks them."""
     K = int(args.num_samples)
     if K < 1:
         raise ValueError("--num_samples K must be >= 1")
+    if getattr(args, "kde_nll", 0) and K < 4:
+        raise ValueError("--kde_nll 1 needs --num_samples K >= 4")
     fit_mode = getattr(args, "fit_head", "off") or "off"
     calibrate = bool(getattr(args, "calibration", 0)) or fit_mode != "off"
     plan = left_out_plan(args, params.nmax)
@@ -193,6 +215,17 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
             f"collision rate: samples {res['collision_rate']:.6g} mean {res['collision_rate_pred']:.6g} "
             f"best joint sample {res['collision_rate_best']:.6g} "
             f"ground truth {res['collision_rate_gt']:.6g}")
+    want_kde = bool(getattr(args, "kde_nll", 0))
+    kde_floor = float(getattr(args, "kde_floor", -20.0))
+    kde = None
+    if want_kde:
+        kde = gh.kde_nll(out.pred, t["targets"], t["n_active"], K, seed=args.sample_seed,
+                         log_floor=kde_floor, n_frames=one, ped_mask=t["ped_mask"],
+                         want_per_ped=keep is not None)
+        res.update(kde_figures(kde))
+        log(f"KDE-NLL of the {K} draws on dataset {args.leaveDataset}: {res['kde_nll']:.6g} per pair "
+            f"and step, final step {res['kde_nll_final']:.6g}, floor {kde_floor:g} reached by "
+            f"{res['kde_clipped']:.4f} of the steps")
     calib = None
     if calibrate:
         calib = gh.stats(out.pred, t["targets"], t["n_active"], CALIB_LEVELS, n_frames=one,
@@ -204,7 +237,7 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
             f"ECE {res['ece']:.4f}, q_ratio {res['q_ratio']:.6g}, sigma_x / sigma_y step 1 "
             f"{sig[0, 0]:.6g} / {sig[1, 0]:.6g} step 12 {sig[0, -1]:.6g} / {sig[1, -1]:.6g}")
     fc_mode = getattr(args, "fullcov_head", "off") or "off"
-    fc = fc_st = fc_bk = fc_joint = None
+    fc = fc_st = fc_bk = fc_joint = fc_kde = None
     if fc_mode != "off":
         from .fullcov import FullCovHead
         fc = FullCovHead(device=device)
@@ -240,15 +273,29 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                 f"{res['fullcov_collision_rate']:.6g} (per-step head {res['collision_rate']:.6g}) "
                 f"best joint sample {res['fullcov_collision_rate_best']:.6g} (per-step head "
                 f"{res['collision_rate_best']:.6g})")
+        if want_kde:
+            fc_kde = fc.kde_nll(out.pred, t["targets"], t["n_active"], K, seed=args.sample_seed,
+                                log_floor=kde_floor, n_frames=one, ped_mask=t["ped_mask"],
+                                want_per_ped=keep is not None)
+            res.update(kde_figures(fc_kde, "fullcov_"))
+            log(f"full-covariance KDE-NLL of the {K} draws on dataset {args.leaveDataset}: "
+                f"{res['fullcov_kde_nll']:.6g} per pair and step (per-step head "
+                f"{res['kde_nll']:.6g}), final step {res['fullcov_kde_nll_final']:.6g} (per-step "
+                f"head {res['kde_nll_final']:.6g}), floor {kde_floor:g} reached by "
+                f"{res['fullcov_kde_clipped']:.4f} of the steps")
     if keep is not None:
         keep.update(plan=plan, pred=out.pred, head=gh.head, out=bk, n_frames=np.ones(S, np.int32),
                     joint=joint)
         if calibrate:
             keep.update(calib=calib, fitted=fitted)
+        if kde is not None:
+            keep.update(kde=kde)
         if fc is not None:
             keep.update(fullcov=dict(stats=fc_st, out=fc_bk, fitted=ffit), fullcov_chol=fc.chol)
             if fc_joint is not None:
                 keep["fullcov"]["joint"] = fc_joint
+            if fc_kde is not None:
+                keep["fullcov"]["kde"] = fc_kde
     return res
 
 

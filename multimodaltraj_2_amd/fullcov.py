@@ -11,8 +11,9 @@ parity is unpinned (tests/fullcov_ref.py is the float64 checker).
 second moments, the joint NLL, the innovations q_t and their coverage),
 ``fit`` sets the head to the closed-form maximum-likelihood one, ``sample``
 draws one reproducible trajectory per (scene, frame, pedestrian),
-``best_of_k`` evaluates K such draws against the targets in one launch and
-``joint_eval`` takes them as joint samples of a scene-frame (JADE_K / JFDE_K
+``best_of_k`` evaluates K such draws against the targets in one launch,
+``kde_nll`` scores the targets under a kernel density estimate of the same
+draws (csrc/g2k_kde.hip) and ``joint_eval`` takes them as joint samples of a scene-frame (JADE_K / JFDE_K
 and the collision counts, csrc/g2k_joint.hip), also in one launch."""
 from __future__ import annotations
 
@@ -25,7 +26,8 @@ import torch
 
 from . import _lib
 from .frame_step import OBS_LEN, PRED_LEN, _check_dev, _ptr, _stream
-from .nll import DEFAULT_LEVELS, MAX_LEVELS, _best_of_k, _check_pairs_inputs, _joint_eval
+from .nll import (DEFAULT_LEVELS, MAX_LEVELS, _best_of_k, _check_pairs_inputs, _joint_eval,
+                  _kde_nll)
 
 DIM = 2 * PRED_LEN
 
@@ -284,6 +286,17 @@ class FullCovHead:
         self._check_chol(pred.device)
         return _best_of_k("g2k_fullcov_best_of_k_f32", self.chol, d, pred, targets, n_active, k, seed,
                           n_frames, ped_mask, want_per_ped, want_best, stream)
+
+    def kde_nll(self, pred, targets, n_active, k, seed=0, *, log_floor=-20.0, n_frames=None,
+                ped_mask=None, want_per_ped=False, targets_shared=False, stream=None):
+        """KDE-NLL in one launch (g2k_fullcov_kde_nll_f32): GaussianHead.kde_nll
+        over this head's correlated draws ``sample(pred, seed + i)``, i < k ->
+        nll.KdeNll."""
+        d = self._dims(pred)
+        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
+        self._check_chol(pred.device)
+        return _kde_nll("g2k_fullcov_kde_nll_f32", self.chol, d, pred, targets, n_active, k, seed,
+                        log_floor, n_frames, ped_mask, want_per_ped, stream)
 
     def joint_eval(self, pred, targets, n_active, k, radius, seed=0, *, n_frames=None, ped_mask=None,
                    targets_shared=False, want_per_frame=True, stream=None):

@@ -9,7 +9,9 @@ sigma_y, atanh rho per prediction step) around the model's predictions
 returns the summed loss, the pair count, d nll / d head and (optionally)
 d nll / d pred; ``sample`` draws one reproducible trajectory per
 (step, pedestrian); ``best_of_k`` evaluates K such draws against the targets
-in one launch (minADE_K / minFDE_K, csrc/g2k_bestk.hip); ``joint_eval``
+in one launch (minADE_K / minFDE_K, csrc/g2k_bestk.hip); ``kde_nll`` fits a
+Gaussian kernel density estimate to the same K draws per step and scores the
+target under it (the KDE-NLL of Trajectron++, csrc/g2k_kde.hip); ``joint_eval``
 scores the same K draws as JOINT samples of a scene-frame (JADE_K / JFDE_K)
 and counts collisions between the pedestrians (csrc/g2k_joint.hip);
 ``stats`` measures the head's calibration against the targets (coverage of
@@ -63,6 +65,43 @@ class BestOfK:
     @property
     def fde(self) -> float:
         return self._mean(4)
+
+
+@dataclass
+class KdeNll:
+    """``GaussianHead.kde_nll``'s outputs (include/g2k_hip.h).  Every property
+    is one host read (float64); a figure whose denominator is 0 is NaN."""
+    out: torch.Tensor               # [S, 8] {sum kde_nll, sum kde_nll_final, pairs, sum clipped, K, floor, 0, 0}
+    per_ped: torch.Tensor | None    # [S, F, Nmax, 4] {kde_nll, kde_nll_final, clipped steps, 0}
+    k: int = 0
+    log_floor: float = -20.0
+
+    def totals(self):
+        """The sums over all scenes, on the host (one read, float64)."""
+        return self.out.double().sum(dim=0).tolist()
+
+    def _mean(self, i, per=1):
+        t = self.totals()
+        return t[i] / (t[2] * per) if t[2] > 0 else float("nan")
+
+    @property
+    def pairs(self) -> int:
+        return int(self.totals()[2])
+
+    @property
+    def kde_nll(self) -> float:
+        """Per pair: the mean over the 12 steps of -max(log density, floor)."""
+        return self._mean(0)
+
+    @property
+    def kde_nll_final(self) -> float:
+        """Per pair: the last step's."""
+        return self._mean(1)
+
+    @property
+    def clipped_share(self) -> float:
+        """The share of (pair, step) terms that sit on the floor."""
+        return self._mean(3, PRED_LEN)
 
 
 @dataclass
@@ -264,6 +303,32 @@ def _best_of_k(symbol, head, d, pred, targets, n_active, k, seed, n_frames, ped_
     return BestOfK(sums=sums, per_ped=per_ped, best=best)
 
 
+def _kde_nll(symbol, head, d, pred, targets, n_active, k, seed, log_floor, n_frames, ped_mask,
+             want_per_ped, stream):
+    """The KDE-NLL entry point ``symbol`` (g2k_kde_nll_f32 or
+    g2k_fullcov_kde_nll_f32) on checked inputs; ``head`` is that head's
+    parameter tensor -> KdeNll."""
+    lib = _lib.load()
+    dev = pred.device
+    k = int(k)
+    if not 4 <= k <= 4096:
+        raise ValueError(f"k = {k}: 4..4096")
+    log_floor = float(log_floor)
+    if not math.isfinite(log_floor):
+        raise ValueError(f"log_floor = {log_floor}: finite")
+    S, F, Nmax = d.S, d.F, d.Nmax
+    out = torch.empty((S, 8), dtype=torch.float32, device=dev)
+    per_ped = torch.empty((S, F, Nmax, 4), dtype=torch.float32, device=dev) if want_per_ped else None
+    size = getattr(lib, symbol.replace("_f32", "_workspace_bytes"))
+    ws = torch.empty(max(1, int(size(ctypes.byref(d)))), dtype=torch.uint8, device=dev)
+    rc = getattr(lib, symbol)(ctypes.byref(d), _ptr(pred), _ptr(targets), _ptr(n_active),
+                              _ptr(n_frames), _ptr(ped_mask), _ptr(head),
+                              ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), k, ctypes.c_float(log_floor),
+                              _ptr(per_ped), _ptr(out), _ptr(ws), ws.numel(), _stream(stream))
+    _lib.check(symbol, rc)
+    return KdeNll(out=out, per_ped=per_ped, k=k, log_floor=log_floor)
+
+
 def _joint_eval(symbol, head, d, pred, targets, n_active, k, radius, seed, n_frames, ped_mask,
                 want_per_frame, stream, gpu_only=False):
     """The joint best-of-K entry point ``symbol`` (g2k_joint_eval_f32 or
@@ -342,6 +407,19 @@ class GaussianHead:
         _check_dev("head", self.head, pred.device, torch.float32)
         return _best_of_k("g2k_best_of_k_f32", self.head, d, pred, targets, n_active, k, seed,
                           n_frames, ped_mask, want_per_ped, want_best, stream)
+
+    def kde_nll(self, pred, targets, n_active, k, seed=0, *, log_floor=-20.0, n_frames=None,
+                ped_mask=None, want_per_ped=False, targets_shared=False, stream=None):
+        """KDE-NLL in one launch (g2k_kde_nll_f32): per pair and step a
+        Gaussian kernel density estimate (Scott's bandwidth, as
+        scipy.stats.gaussian_kde) of the K draws ``sample(pred, seed + i)``,
+        i < k, and the target's log density under it, floored at ``log_floor``
+        -> KdeNll.  k in 4..4096."""
+        d = self._dims(pred)
+        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
+        _check_dev("head", self.head, pred.device, torch.float32)
+        return _kde_nll("g2k_kde_nll_f32", self.head, d, pred, targets, n_active, k, seed, log_floor,
+                        n_frames, ped_mask, want_per_ped, stream)
 
     def joint_eval(self, pred, targets, n_active, k, radius, seed=0, *, n_frames=None, ped_mask=None,
                    targets_shared=False, want_per_frame=True, stream=None):
