@@ -686,6 +686,25 @@ int g2k_fullcov_kde_nll_f32(const g2k_dims* d, const float* pred, const float* t
                             float log_floor, float* per_ped, float* out, void* workspace,
                             int64_t workspace_bytes, void* stream);
 
+/*
+ * The launch geometry of the per-pair sampled evaluations (added after ABI 11;
+ * detect by symbol): what g2k_best_of_k_f32, g2k_fullcov_best_of_k_f32,
+ * g2k_kde_nll_f32 and g2k_fullcov_kde_nll_f32 work out from d->S, F, Nmax and
+ * K before they launch, returned instead of launched.  Host arithmetic only,
+ * no HIP call.  out[G2K_BESTK_GEOM_FIELDS]:
+ *   G2K_BESTK_GEOM_KS  lanes that share a pair's K draws (a power of two <= 64
+ *                      and <= K, doubled while S F Nmax KS < 2 * 256 * 1024)
+ *   G2K_BESTK_GEOM_FC  frames per workgroup (256 / (Nmax KS), 1..F)
+ *   G2K_BESTK_GEOM_C   workgroups per scene (ceil(F / FC); 1 when F = 0)
+ * Returns G2K_OK, or G2K_EINVAL for a NULL d or out, S < 0, F < 0, Nmax outside
+ * 1..256 or K outside 1..4096 (the KDE pair itself takes K from 4).
+ */
+#define G2K_BESTK_GEOM_KS 0
+#define G2K_BESTK_GEOM_FC 1
+#define G2K_BESTK_GEOM_C 2
+#define G2K_BESTK_GEOM_FIELDS 3
+int g2k_best_of_k_geometry(const g2k_dims* d, int32_t K, int32_t* out);
+
 int64_t g2k_context_conv_workspace_bytes(int32_t Hh, int32_t Ww, int32_t D);
 int g2k_context_conv_f32(const float* img, int32_t Hh, int32_t Ww, int32_t C, const float* filt,
                          int32_t D, float lambda, float* out, float* G, void* workspace,

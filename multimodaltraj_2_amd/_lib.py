@@ -38,6 +38,8 @@ STEP_MAX_SPLIT = 4
 GEOM_FIELDS = ("tpw", "np", "fc", "chunks", "dwo_seq", "own0", "split", "variant", "lds_bytes",
                "ped_major")
 STEP_VARIANTS = ("general", "nll", "inv", "blk")
+# g2k_best_of_k_geometry's out[] (G2K_BESTK_GEOM_*)
+BESTK_GEOM_FIELDS = ("ks", "fc", "c")
 
 
 class G2KWeights(ctypes.Structure):
@@ -113,6 +115,7 @@ SYMBOLS = {
     "g2k_fullcov_kde_nll_f32": (c_int, [ctypes.POINTER(G2KDims), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                         ctypes.c_uint64, c_i32, c_f32, c_vp, c_vp, c_vp, c_i64,
                                         c_vp]),
+    "g2k_best_of_k_geometry": (c_int, [ctypes.POINTER(G2KDims), c_i32, ctypes.POINTER(c_i32)]),
     "g2k_step_grad_update_f32": (c_int, [ctypes.POINTER(G2KDims), ctypes.POINTER(G2KWeights),
                                          c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp,
                                          c_vp, c_i64, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp]),

@@ -5,6 +5,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 
+#include "g2k_bestk_geom.h"
 #include "g2k_common.h"
 
 namespace g2k {
@@ -580,6 +581,21 @@ int64_t g2k_best_of_k_workspace_bytes(const g2k_dims* d) { return sampled_ws_byt
 int64_t g2k_fullcov_best_of_k_workspace_bytes(const g2k_dims* d) { return sampled_ws_bytes(d, false); }
 int64_t g2k_joint_eval_workspace_bytes(const g2k_dims* d) { return sampled_ws_bytes(d, true); }
 int64_t g2k_fullcov_joint_eval_workspace_bytes(const g2k_dims* d) { return sampled_ws_bytes(d, true); }
+
+// the launch geometry of the per-pair sampled evaluations (bestk_geom: host
+// arithmetic, no HIP call), as the launchers work it out
+int g2k_best_of_k_geometry(const g2k_dims* d, int32_t K, int32_t* out) {
+  if (!d) return set_err(G2K_EINVAL, "dims is NULL");
+  if (d->S < 0 || d->F < 0 || d->Nmax < 1 || d->Nmax > kMaxN)
+    return set_err(G2K_EINVAL, "S=%d F=%d Nmax=%d", d->S, d->F, d->Nmax);
+  if (K < 1 || K > 4096) return set_err(G2K_EINVAL, "K=%d (1..4096)", K);
+  if (!out) return set_err(G2K_EINVAL, "out is NULL");
+  const BestkGeom g = bestk_geom(*d, K);
+  out[0] = 1 << g.ks_log2;
+  out[1] = g.FC;
+  out[2] = g.C;
+  return G2K_OK;
+}
 
 int g2k_best_of_k_f32(const g2k_dims* d, const float* pred, const float* targets,
                       const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,

@@ -279,6 +279,18 @@ def _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_
         _check_dev("ped_mask", ped_mask, dev, torch.uint8)
 
 
+def best_of_k_geometry(S, F, Nmax, k) -> dict:
+    """The launch geometry of the per-pair sampled evaluations (best-of-K and
+    KDE-NLL of either head) for these shapes (g2k_best_of_k_geometry: host
+    arithmetic, no HIP call): ks lanes share a pair's draws, fc frames per
+    workgroup, c workgroups per scene."""
+    lib = _lib.load()
+    d = _lib.G2KDims(S, F, OBS_LEN, PRED_LEN, 16, 64, Nmax, OBS_LEN, 0)
+    out = (ctypes.c_int32 * len(_lib.BESTK_GEOM_FIELDS))()
+    _lib.check("g2k_best_of_k_geometry", lib.g2k_best_of_k_geometry(ctypes.byref(d), int(k), out))
+    return dict(zip(_lib.BESTK_GEOM_FIELDS, (int(v) for v in out)))
+
+
 def _best_of_k(symbol, head, d, pred, targets, n_active, k, seed, n_frames, ped_mask, want_per_ped,
                want_best, stream):
     """The marginal best-of-K entry point ``symbol`` (g2k_best_of_k_f32 or

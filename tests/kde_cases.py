@@ -10,6 +10,7 @@ import functools
 import numpy as np
 
 from oracle import g2k_ref as ref
+from tests import eval_cells as ec
 from tests import fullcov_ref
 from tests.bestk_ref import MASK64, pair_mask
 
@@ -26,6 +27,9 @@ CASES = [
     ("k4",     2, 2, 8,  4,   [8, 5],      [2, 2],    True,  False, False),  # the minimum K
     ("shared", 2, 3, 16, 8,   [16, 9],     [3, 2],    True,  True,  False),  # G2K_STEP_TARGETS_SHARED
     ("far",    2, 2, 16, 20,  [16, 11],    None,      False, False, True),   # targets >= 4 sigma away: clips
+    # tests/eval_cells.py "ks32-fill": KS 32 cut by the fill limit (K alone would give 64), two
+    # chunks per scene and S 8 > 256: the rows kernel's second workgroup
+    ("ks32fill", 33, 2, 256, 64, list(ec.KS32_N_ACTIVE), list(ec.KS32_N_FRAMES), True, False, False),
 ]
 IDS = [c[0] for c in CASES]
 

@@ -281,6 +281,31 @@ def test_step_geometry_validates_and_agrees_with_the_planning_calls():
     assert (g["variant"], g["tpw"], g["np"], g["ped_major"]) == ("nll", 1, 8, 1)
 
 
+def test_best_of_k_geometry_validates():
+    """g2k_best_of_k_geometry (added after ABI 11: by symbol; host arithmetic,
+    no HIP call): NULL dims / out and the sizes the evaluations reject are
+    G2K_EINVAL; out[] is {KS, FC, C} of bestk_geom."""
+    lib = _lib.load()
+    assert lib.g2k_abi_version() == 11 and _lib.ABI_VERSION == 11
+    out = (ctypes.c_int32 * len(_lib.BESTK_GEOM_FIELDS))(-7, -7, -7)
+
+    def call(d, K=20, o=out):
+        return lib.g2k_best_of_k_geometry(ctypes.byref(d) if d is not None else None, K, o)
+    assert call(None) == -1 and b"dims is NULL" in lib.g2k_last_error()
+    assert call(_dims(), o=None) == -1 and b"out is NULL" in lib.g2k_last_error()
+    for bad in (dict(S=-1), dict(F=-1), dict(Nmax=0), dict(Nmax=257)):
+        assert call(_dims(**bad)) == -1, bad
+    for K in (0, -1, 4097):
+        assert call(_dims(), K=K) == -1 and b"K=%d " % K in lib.g2k_last_error()
+    assert list(out) == [-7, -7, -7]                       # a rejected call writes nothing
+    # T, L, D, H and the flags are not looked at
+    assert call(_dims(T=9, L=10, D=3, H=5, flags=_lib.STEP_TARGETS_SHARED)) == 0
+    assert list(out) == [16, 1, 20]                        # 1280 slots: K = 20 stops KS at 16
+    assert call(_dims(S=256)) == 0 and list(out) == [4, 2, 10]
+    assert call(_dims(S=0)) == 0 and list(out) == [16, 1, 20]
+    assert call(_dims(F=0), K=1) == 0 and list(out) == [1, 1, 1]
+
+
 def test_loop_invariant_launches_hold_one_ring_slot():
     """Stride 0 with shared targets and one workgroup per scene
     (g2k_scene.hip frames_invariant): the forward forms one head per chunk,

@@ -57,7 +57,8 @@ g2k_nll_f32
   NULL / [3, 0, 2, 1]; ped_mask NULL / scene 0 all zero; head r in [-3, 3]
   with r[0] = 3, r[1] = -3 (c = 1 - rho^2 = 9.9e-3: the cancellation costs
   ~2 rho ulp(rho) / c ~ 1e-5 relative, inside 1e-4; measured below).  One
-  launch without any pair.
+  launch without any pair.  S 257, F 1, Nmax 3 (tests/eval_cells.py
+  "nll-rows257"): 257 rows, the second trip of g2k_grad_rows_kernel's r0 loop.
 g2k_gauss_sample_f32
   (S, F, Nmax) (1, 1, 1) / (2, 3, 7) / (1, 2, 256) x seeds 0, 2^32 - 1, 2^32,
   2^64 - 1 (both halves of the 64-bit seed, carries between them).
@@ -98,6 +99,7 @@ import torch
 
 from multimodaltraj_2_amd import _lib
 from oracle import g2k_ref as ref
+from tests import eval_cells as ec
 from tests.abi_arena import Arena, all_written, untouched
 from tests.conftest import close, close_h
 
@@ -565,6 +567,42 @@ def test_nll_domain(lib, Nmax, framed, masked):
     print(f"nll Nmax={Nmax} framed={framed} masked={masked}: nll {e_nll:.2e} dhead {e_dh:.2e} "
           f"dpred {e_dp:.2e} (bound 1e-4)")
     assert int(out[37]) == R_pairs
+    assert e_nll <= TOL and e_dh <= TOL and e_dp <= TOL
+
+
+def test_nll_rows_past_one_trip(lib):
+    """tests/eval_cells.py "nll-rows257": S 257 scenes leave 257 rows [38], so
+    g2k_grad_rows_kernel takes a second trip of its r0 loop with one real row
+    and clamped loads past it (S 257 is the smallest that does; F 1 and Nmax 3
+    keep the oracle quick).  n_active 0..3, a mask, the head of test_nll_domain.
+    MEASURED on an MI355X, error / bound (1e-4): nll 0.037, head gradient 0.058
+    (normwise), dpred 0.096; 281 pairs, the count exact."""
+    c = ec.NLL
+    S, F, Nmax = c.S, c.F, c.Nmax
+    rng = np.random.default_rng(8200)
+    n_active = [int(v) for v in rng.integers(0, Nmax + 1, S)]
+    n_active[0], n_active[S - 1] = Nmax, Nmax            # the last row (the second trip's) counts
+    mask = (rng.random((S, Nmax)) > 0.3).astype(np.uint8)
+    mask[S - 1] = 1
+    pred, tgt = error_inputs(rng, S, F, Nmax, n_active, None)
+    head = draw_head(rng)
+    out, dpred = run_nll(lib, pred, tgt, n_active, None, mask, head)
+    R_nll, R_pairs, R_dh, R_dp = 0.0, 0, np.zeros((3, 12)), []
+    last = None
+    for s in range(S):
+        l_, p_, h_, d_ = ref.bivariate_nll(pred[s], tgt[s], head, n_active[s], F, mask[s].astype(bool))
+        R_nll += l_
+        R_pairs += p_
+        R_dh += h_
+        R_dp.append(d_)
+        last = (l_, p_)
+    assert last[1] == Nmax and abs(last[0]) > 1e-3 * abs(R_nll) / S      # dropping row 256 would show
+    e_nll = abs(float(out[36]) - R_nll) / abs(R_nll)
+    e_dh = np.abs(out[:36].reshape(3, 12) - R_dh).max() / np.abs(R_dh).max()
+    e_dp = check_dpred_footprint(dpred, R_dp, n_active, None, mask)
+    print(f"nll-rows257: worst error / bound: nll {e_nll / TOL:.2g} dhead {e_dh / TOL:.2g} "
+          f"dpred {e_dp / TOL:.2g}; {R_pairs} pairs")
+    assert int(out[37]) == R_pairs                        # exact: one pair short shows a lost row
     assert e_nll <= TOL and e_dh <= TOL and e_dp <= TOL
 
 

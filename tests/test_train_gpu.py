@@ -12,6 +12,7 @@ from multimodaltraj_2_amd import frame_step as fs
 from multimodaltraj_2_amd import train_step as ts
 from multimodaltraj_2_amd.synthetic import CONFIGS, make_batch
 from oracle import g2k_ref as ref
+from tests import eval_cells as ec
 from tests.conftest import close
 
 pytestmark = pytest.mark.gpu
@@ -199,6 +200,132 @@ def test_train_config_shape_matches_oracle(gpu, name, S):
             assert np.abs(rows[s, :P] - r).max() <= TOL * np.abs(r).max(), s
             assert abs(rows[s, P] - l) <= TOL * l and rows[s, P + 1] == cn
     _check_grad(g, loss, cnt, R, Nmax)
+
+
+@pytest.mark.parametrize("cell", ec.TRAIN, ids=lambda c: c.id)
+def test_grad_rows_past_one_trip_match_oracle(gpu, cell):
+    """tests/eval_cells.py TRAIN: more than 256 gradient rows, so
+    g2k_grad_rows_kernel takes a second (rows260) and a third (rows516) trip
+    of its r0 loop, each with four real rows and clamped loads past the last
+    one (tests/test_eval_cells.py proves the row counts; every other case of
+    this file stays at 256 rows or fewer).  S 65 / 129 with an explicit split
+    of 4 are the smallest launches past 256 and past 512 rows; Nmax 7, F 5,
+    H 64 keep the oracle quick.  n_frames includes 0, 1 and 3 < split: scenes
+    whose workgroups leave zero rows.  Against the oracle: the all-scene sum
+    [P + 2] and every 16th scene's own rows, through both entry points and
+    through the kernel's UPD build (the folded update); pred and h of the train
+    launch bit-identical to the forward step's; two launches bit-identical with
+    the workspace poisoned in between.
+
+    MEASURED on an MI355X, worst error / bound (printed before the
+    assertions), rows260 / rows516: gradient blocks <= 0.0022 / 0.0021, loss
+    0.00012 / 0.00011, a scene's own rows 0.0016 / 0.0021, the folded update's
+    parameters 0.029 / 0.029 and mean squares 0.015 / 0.0088; the train
+    launch's figures equal the gradient-only launch's."""
+    S, X, Nmax, F, H = cell.S, cell.split, cell.Nmax, cell.F, cell.H
+    lam, lr, decay, clip = 0.05, 5e-3, 0.95, 10.0
+    b, params, t = _train_batch(gpu, S, Nmax, H, F=F, seed=31)
+    nfr, mask = ec.train_n_frames(cell), ec.train_mask(cell)
+    kw = dict(n_frames=torch.from_numpy(nfr).to(gpu),
+              ped_mask=torch.from_numpy(mask.astype(np.uint8)).to(gpu), lam=lam, split=X)
+    args = (t["pos"], t["vislet"], t["G"], t["targets"], t["n_active"])
+    P = ts.grad_size(Nmax)
+
+    # the oracle: the all-scene sum and every scene's own gradient
+    w = params.numpy()
+    loss, cnt, R = 0.0, 0, {k: np.zeros(np.shape(w[k])) for k in ref.GRAD_ORDER}
+    own = {}
+    for s in range(S):
+        l, c, g = ref.scene_loss_grad(b.pos[s], b.vislet[s], b.G[s], w, b.targets[s], b.n_active[s],
+                                      n_frames=int(nfr[s]), lam=lam, ped_mask=mask[s])
+        loss += l
+        cnt += c
+        for k in R:
+            R[k] += g[k]
+        if s % 16 == 0:
+            own[s] = (l, c, np.concatenate([np.asarray(g[k]).reshape(-1) for k in ref.GRAD_ORDER]))
+
+    ratios = {}
+
+    def check_rows(ws, tag):
+        assert ws.numel() >= S * X * (P + 2) * 4
+        rows = (ws[:S * X * (P + 2) * 4].view(torch.float32).reshape(S, X, P + 2).double().sum(1)
+                .cpu().numpy())
+        for s, (l, c, r) in own.items():
+            if c == 0:                                     # no frame: the workgroups leave zero rows
+                assert np.all(r == 0) and l == 0 and np.all(rows[s] == 0), s
+                continue
+            ratios[f"rows-{tag}"] = max(ratios.get(f"rows-{tag}", 0.0),
+                                        float(np.abs(rows[s, :P] - r).max() / (TOL * np.abs(r).max())),
+                                        abs(rows[s, P] - l) / (TOL * l))
+            assert rows[s, P + 1] == c, s
+
+    def check_sum(g, tag):
+        off = 0
+        for k in ref.GRAD_ORDER:
+            r = R[k].reshape(-1)
+            got = g[off:off + r.size]
+            off += r.size
+            if k == "Wr":
+                assert np.all(got == 0)
+            else:
+                ratios[f"{k}-{tag}"] = float(np.abs(got - r).max() / (TOL * np.abs(r).max()))
+        ratios[f"loss-{tag}"] = abs(g[P] - loss) / (TOL * loss)
+        assert g[P + 1] == cnt
+
+    # g2k_step_grad_f32 (the <false> build), twice, the workspace poisoned in between
+    gp = ts.GradPlan(params, *args, **kw)
+    g1 = gp.run().clone()
+    torch.cuda.synchronize()
+    check_rows(gp._ws, "grad")
+    gp._ws.random_(0, 256)
+    g2 = gp.run().clone()
+    torch.cuda.synchronize()
+    assert torch.equal(g1, g2)
+    check_sum(g1.double().cpu().numpy(), "grad")
+
+    # g2k_step_grad_update_f32 (the <true> build): run() + optimizer_update, bit for bit,
+    # and the oracle's update
+    out = []
+    for fused in (False, True):
+        flat, views = ts.flat_params(params)
+        ms = torch.full_like(flat, 0.25)
+        p0 = flat.cpu().numpy().copy()
+        plan = ts.GradPlan(views, *args, **kw)
+        if fused:
+            g = plan.run_update(flat, ms, lr=lr, decay=decay, grad_clip=clip)
+        else:
+            g = plan.run()
+            ts.optimizer_update(flat, g, lr=lr, decay=decay, grad_clip=clip, ms=ms)
+        torch.cuda.synchronize()
+        out.append((g.clone(), flat.clone(), ms.clone()))
+    (ga, pa, ma), (gb, pb, mb) = out
+    assert torch.equal(ga, g1) and torch.equal(ga, gb) and torch.equal(pa, pb) and torch.equal(ma, mb)
+    # (the oracle's update rule on the launch's own gradient, which check_sum holds to the
+    # oracle's: test_update_matches_oracle's bounds are for one gradient fed to both sides)
+    gh = gb.cpu().numpy()
+    rp, rm = ref.optimizer_update(p0, np.full(P, 0.25, np.float32), gh[:P], gh[P + 1], lr, decay, clip)
+    ratios["update-params"] = float(np.abs(pb.cpu().numpy() - rp).max() / (1e-6 * max(1.0, np.abs(rp).max())))
+    ratios["update-ms"] = float(np.abs(mb.cpu().numpy() - rm).max() / (1e-5 * np.abs(rm).max()))
+
+    # g2k_train_step_f32: the same rows kernel behind the train launch; pred and h the forward step's
+    tp = ts.TrainPlan(params, *args, t["h0"], **kw)
+    gt1 = tp.run().clone()
+    torch.cuda.synchronize()
+    check_rows(tp._ws, "train")
+    pred1, h1 = tp.out.pred.clone(), tp.out.h.clone()
+    tp._ws.random_(0, 256)
+    gt2 = tp.run().clone()
+    torch.cuda.synchronize()
+    assert torch.equal(gt1, gt2) and torch.equal(pred1, tp.out.pred) and torch.equal(h1, tp.out.h)
+    check_sum(gt1.double().cpu().numpy(), "train")
+    fwd = fs.step_fused(params, *args, t["h0"], **kw)
+    torch.cuda.synchronize()
+    assert torch.equal(fwd.pred, pred1) and torch.equal(fwd.h, h1)
+    worst = max(ratios, key=ratios.get)
+    print(f"{cell.id}: worst error / bound = {ratios[worst]:.3g} ({worst}); "
+          + ", ".join(f"{k} {v:.2g}" for k, v in sorted(ratios.items())))
+    assert all(v <= 1.0 for v in ratios.values()), ratios
 
 
 def test_train_step_world2_branch_matches_one_rank(gpu, monkeypatch):
