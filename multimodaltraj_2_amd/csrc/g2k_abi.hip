@@ -103,6 +103,18 @@ int validate_H(int H) {
 }
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+bool aligned4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
+
+// outputs of the fused step that the recurrence and the pedestrian-major
+// prediction stores (16 bytes per lane) reach
+int validate_step_outputs(const g2k_dims* d, const float* h_in, const float* h_out,
+                          const float* pred) {
+  if (!aligned16(h_in) || !aligned16(h_out))
+    return set_err(G2K_EINVAL, "h_in and h_out must be 16-byte aligned");
+  if ((d->flags & G2K_STEP_PRED_PED_MAJOR) && !aligned16(pred))
+    return set_err(G2K_EINVAL, "pred must be 16-byte aligned with G2K_STEP_PRED_PED_MAJOR");
+  return G2K_OK;
+}
 
 // inputs of the fused step (reference and train mode)
 int validate_step_inputs(const g2k_dims* d, const g2k_weights* w, const float* pos,
@@ -157,6 +169,10 @@ int train_launch(StepArgs a, float* grad, void* workspace, int64_t workspace_byt
   const int width = grad_params(a.d.Nmax, loss_nll(a.d)) + 2;
   if (!grad) return set_err(G2K_EINVAL, "grad is NULL");
   if (loss_nll(a.d) && !a.w.head) return set_err(G2K_EINVAL, "G2K_STEP_LOSS_NLL needs weights->head");
+  // gradient rows (floats), the update's ticket line and the scene tickets
+  // (ints, agent-scope fetch-adds) at multiples of 4 bytes from its start
+  if (workspace && !aligned4(workspace))
+    return set_err(G2K_EINVAL, "workspace must be 4-byte aligned");
   const int64_t need = grad_rows_bytes(&a.d);
   if (!workspace || workspace_bytes < need)
     return set_err(G2K_EINVAL, "workspace of %lld bytes needed for %d workgroups per scene (got %lld)",
@@ -255,9 +271,11 @@ int g2k_step_fused_f32(const g2k_dims* d, const g2k_weights* w, const float* pos
   if ((rc = validate_H(d->H))) return rc;
   if (!h_in || !h_out || !pred || !metrics)
     return set_err(G2K_EINVAL, "a required buffer pointer is NULL");
-  if (!aligned16(h_in) || !aligned16(h_out))
-    return set_err(G2K_EINVAL, "h_in and h_out must be 16-byte aligned");
+  if ((rc = validate_step_outputs(d, h_in, h_out, pred))) return rc;
   if (workspace_bytes < 0) return set_err(G2K_EINVAL, "negative workspace size");
+  // scene tickets (agent-scope fetch-adds) and float partials are carved from it
+  if (workspace && !aligned4(workspace))
+    return set_err(G2K_EINVAL, "workspace must be 4-byte aligned");
   if (d->S == 0) return G2K_OK;
   StepArgs a = step_args(d, w, pos, vislet, G, targets, n_active, n_frames, ped_mask, lambda,
                          (hipStream_t)stream);
@@ -288,8 +306,7 @@ int g2k_train_step_f32(const g2k_dims* d, const g2k_weights* w, const float* pos
   if ((rc = validate_H(d->H))) return rc;
   if (!h_in || !h_out || !pred || !metrics)
     return set_err(G2K_EINVAL, "a required buffer pointer is NULL");
-  if (!aligned16(h_in) || !aligned16(h_out))
-    return set_err(G2K_EINVAL, "h_in and h_out must be 16-byte aligned");
+  if ((rc = validate_step_outputs(d, h_in, h_out, pred))) return rc;
   StepArgs a = step_args(d, w, pos, vislet, G, targets, n_active, n_frames, ped_mask, lambda,
                          (hipStream_t)stream);
   a.h_in = h_in; a.h_out = h_out; a.pred = pred; a.metrics = metrics;
@@ -481,6 +498,8 @@ int g2k_nll_f32(const g2k_dims* d, const float* pred, const float* targets,
   if (rc) return rc;
   if (!targets || !out) return set_err(G2K_EINVAL, "a required buffer pointer is NULL");
   if (((uintptr_t)targets) & 7) return set_err(G2K_EINVAL, "targets must be 8-byte aligned");
+  if (workspace && !aligned4(workspace))
+    return set_err(G2K_EINVAL, "workspace must be 4-byte aligned");   // rows of floats
   const int64_t need = g2k_nll_workspace_bytes(d);
   if (!workspace || workspace_bytes < need)
     return set_err(G2K_EINVAL, "workspace of %lld bytes needed (got %lld)", (long long)need,
@@ -537,9 +556,13 @@ static int validate_sampled(const char* name, SampledKind kind, const g2k_dims* 
   if (((uintptr_t)targets) & 7) return set_err(G2K_EINVAL, "targets must be 8-byte aligned");
   if (joint && (((uintptr_t)out2) & 7)) return set_err(G2K_EINVAL, "sums_i must be 8-byte aligned");
   if (!joint && (((uintptr_t)out2) & 15)) return set_err(G2K_EINVAL, "per_ped must be 16-byte aligned");
+  // rows of floats (the marginal and KDE pairs) or of int32 (the joint pair):
+  // a workspace that is named is held to it, an empty batch's too
+  if (workspace && (((uintptr_t)workspace) & 3))
+    return set_err(G2K_EINVAL, "workspace must be 4-byte aligned");
   const int64_t need = joint ? joint_eval_ws_bytes(d)
                              : kind == kSampledKde ? kde_nll_ws_bytes(d) : best_of_k_ws_bytes(d);
-  if (d->S > 0 && (!workspace || workspace_bytes < need || (joint && (((uintptr_t)workspace) & 3))))
+  if (d->S > 0 && (!workspace || workspace_bytes < need))
     return set_err(G2K_EINVAL, "workspace of %lld bytes needed (got %lld)%s", (long long)need,
                    (long long)workspace_bytes, joint ? ", 4-byte aligned" : "");
   return G2K_OK;
@@ -700,8 +723,12 @@ static int validate_stats(const char* name, const char* head_name, bool has_mome
   if ((((uintptr_t)moments) | ((uintptr_t)stats) | ((uintptr_t)inside) | ((uintptr_t)r2)) & 7)
     return set_err(G2K_EINVAL, "%sstats, inside and r2 must be 8-byte aligned",
                    has_moments ? "moments, " : "");
+  // slices of doubles and int64 counts: a workspace that is named is held to
+  // it, whether or not this launch needs one
+  if (workspace && (((uintptr_t)workspace) & 7))
+    return set_err(G2K_EINVAL, "workspace must be 8-byte aligned");
   const int64_t need = ws_bytes(d, n_levels);
-  if (d->S > 0 && need > 0 && (!workspace || workspace_bytes < need || (((uintptr_t)workspace) & 7)))
+  if (d->S > 0 && need > 0 && (!workspace || workspace_bytes < need))
     return set_err(G2K_EINVAL, "workspace of %lld bytes needed (got %lld), 8-byte aligned",
                    (long long)need, (long long)workspace_bytes);
   return G2K_OK;
@@ -773,6 +800,8 @@ int g2k_context_conv_f32(const float* img, int32_t Hh, int32_t Ww, int32_t C, co
   if (C < 1 || C > 4) return set_err(G2K_EUNSUPPORTED, "C=%d channels (1..4)", C);
   const int64_t need = g2k_context_conv_workspace_bytes(Hh, Ww, D);
   if (need < 0) return set_err(G2K_EINVAL, "image %dx%d, D=%d (D in 1..16, image >= D)", Hh, Ww, D);
+  if (workspace && !aligned4(workspace))
+    return set_err(G2K_EINVAL, "workspace must be 4-byte aligned");   // partial sums, floats
   if (!workspace || workspace_bytes < need)
     return set_err(G2K_EINVAL, "workspace of %lld bytes needed", (long long)need);
   return ctx_conv_launch(img, Hh, Ww, C, filt, D, lambda, out, G, static_cast<float*>(workspace),

@@ -76,11 +76,13 @@ extern "C" int g2k_scene_gather_f32(const float* xy, const float* vis, int64_t c
   if (S < 0 || F < 1 || Nmax < 1 || Nmax > kMaxN || cols < 1)
     return set_err(G2K_EINVAL, "g2k_scene_gather_f32: S=%d F=%d Nmax=%d cols=%lld", S, F, Nmax,
                    (long long)cols);
+  // (a NULL pointer is aligned: an empty batch may leave its buffers out, but
+  // a buffer it names is held to the same rule as any other)
+  if (((uintptr_t)xy & 7u) || ((uintptr_t)pos & 7u) || ((uintptr_t)targets & 7u))
+    return set_err(G2K_EINVAL, "g2k_scene_gather_f32: xy / pos / targets must be 8-byte aligned");
   if (S == 0) return G2K_OK;
   if (!xy || !pos_col || !tgt_col || !n_active || !pos || !vislet || !targets || !ped_mask)
     return set_err(G2K_EINVAL, "g2k_scene_gather_f32: a required pointer is NULL");
-  if (((uintptr_t)xy & 7u) || ((uintptr_t)pos & 7u) || ((uintptr_t)targets & 7u))
-    return set_err(G2K_EINVAL, "g2k_scene_gather_f32: xy / pos / targets must be 8-byte aligned");
   GatherArgs a{xy, vis, cols, pos_col, tgt_col, vis_off, n_active, S, F, Nmax,
                pos, vislet, targets, ped_mask};
   hipLaunchKernelGGL(g2k_gather_kernel, dim3(S), dim3(256), 0, (hipStream_t)stream, a);

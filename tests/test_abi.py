@@ -409,7 +409,7 @@ def test_sampled_evaluation_entry_points_validate(fn, short, joint):
         c.rejects(_EINVAL, b"targets", d, targets=20, sums_i=20)
         c.rejects(_EINVAL, b"sums_i", d, sums_i=20, ws=None)        # alignment before the workspace
         c.rejects(_EINVAL, b"4-byte aligned", d, ws=18)
-        assert c.rc(_dims(S=0), ws=18, ws_bytes=0) == 0            # ... looked at only when S > 0
+        c.rejects(_EINVAL, b"4-byte aligned", _dims(S=0), ws=18, ws_bytes=0)   # ... an empty batch's too
     else:
         c.rejects(_EINVAL, b"per_ped must be 16-byte aligned", d, per_ped=24)
         c.rejects(_EINVAL, b"targets", d, targets=20, per_ped=24)
