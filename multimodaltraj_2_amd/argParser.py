@@ -3,7 +3,8 @@ the build's own: --data_root (Q8), --device, --mode,
 --world_size, --n_max, --train_batch, --train_scenes, --valid_from_seed,
 --log_dir, --save_dir, --seed, --use_grid_lstm, --loss, --num_samples,
 --sample_seed, --head_log_sigma, --collision_radius, --fit_head,
---calibration, --fullcov_head, --kde_nll, --kde_floor."""
+--calibration, --fullcov_head, --mixture_head, --mixture_components,
+--mixture_iters, --kde_nll, --kde_floor."""
 import argparse
 
 
@@ -79,6 +80,18 @@ class ArgsParser:
                              'datasets (train; honours --train_scenes) or of the left-out dataset '
                              'itself (eval: in-sample, a bound), and report its minADE_K / minFDE_K, '
                              'joint NLL, coverage and the lag-1 correlation of the residuals')
+    parser.add_argument('--mixture_head', choices=('off', 'train', 'eval'), default='off',
+                        help='--num_samples: after --fullcov_head\'s figures, also fit the '
+                             'Gaussian-mixture trajectory head (--mixture_components full-covariance '
+                             'Gaussians over the 24 residuals, by --mixture_iters EM iterations on the '
+                             "device) on the scenes of the fold's training datasets (train; honours "
+                             '--train_scenes) or of the left-out dataset itself (eval: in-sample, a '
+                             'bound), and report its minADE_K / minFDE_K, NLL per pair, live '
+                             'components, largest weight and the log-likelihood gained by EM')
+    parser.add_argument('--mixture_components', type=int, choices=range(1, 9), default=3,
+                        metavar='1..8', help='--mixture_head: components of the mixture')
+    parser.add_argument('--mixture_iters', type=int, default=30,
+                        help='--mixture_head: EM iterations')
     parser.add_argument('--kde_nll', type=int, choices=(0, 1), default=0,
                         help='--num_samples K (K >= 4): 1 also reports the KDE-NLL of the K draws '
                              '(per step a Gaussian kernel density estimate of the drawn positions, '

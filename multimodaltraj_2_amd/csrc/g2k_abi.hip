@@ -7,6 +7,7 @@
 
 #include "g2k_bestk_geom.h"
 #include "g2k_common.h"
+#include "g2k_mix.h"
 
 namespace g2k {
 
@@ -778,6 +779,80 @@ int g2k_fullcov_sample_f32(const g2k_dims* d, const float* pred, const float* ch
   if (!out) return set_err(G2K_EINVAL, "out is NULL");
   if ((int64_t)d->S * d->F * kL * d->Nmax == 0) return G2K_OK;
   return fullcov_sample_launch(d, pred, chol, seed, out, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------
+// the Gaussian-mixture head (include/g2k_mix.h; added after ABI 11: by symbol)
+// ---------------------------------------------------------------------------
+static bool mix_sizes_ok(const g2k_dims* d) {
+  if (!head_stats_sizes_ok(d, 0)) return false;
+  return (int64_t)d->S * d->F * d->Nmax <= 0x7fffffff;     // slots are indexed in 32 bits per workgroup
+}
+
+int64_t g2k_mix_em_workspace_bytes(const g2k_dims* d) {
+  if (!d || !mix_sizes_ok(d)) return -1;
+  return mix_em_ws_bytes(d);
+}
+
+int g2k_mix_em_f32(const g2k_dims* d, const float* pred, const float* targets,
+                   const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                   const float* mix_in, double* moments, double* resp, double* total,
+                   float* mix_out, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!d) return set_err(G2K_EINVAL, "dims is NULL");
+  if (d->flags & G2K_STEP_PRED_PED_MAJOR)
+    return set_err(G2K_EUNSUPPORTED, "mix_em reads pred_path_band [S, F, 2L, Nmax]");
+  if (!mix_sizes_ok(d))
+    return set_err(G2K_EINVAL, "S=%d F=%d Nmax=%d (Nmax 1..256, S F Nmax < 2^31)", d->S, d->F,
+                   d->Nmax);
+  const struct { const void* p; const char* name; } req[] = {
+      {pred, "pred"}, {targets, "targets"}, {n_active, "n_active"}, {mix_in, "mix_in"},
+      {moments, "moments"}, {resp, "resp"}, {total, "total"}};
+  for (const auto& r : req)
+    if (!r.p) return set_err(G2K_EINVAL, "%s is NULL", r.name);
+  if (((uintptr_t)targets) & 7) return set_err(G2K_EINVAL, "targets must be 8-byte aligned");
+  if ((((uintptr_t)moments) | ((uintptr_t)resp) | ((uintptr_t)total)) & 7)
+    return set_err(G2K_EINVAL, "moments, resp and total must be 8-byte aligned");
+  if ((((uintptr_t)mix_in) | ((uintptr_t)mix_out)) & 3)
+    return set_err(G2K_EINVAL, "mix_in and mix_out must be 4-byte aligned");
+  if (mix_out) {
+    const uintptr_t a = (uintptr_t)mix_in, b = (uintptr_t)mix_out;
+    const uintptr_t bytes = (uintptr_t)G2K_MIX_SLOTS * G2K_MIX_PITCH * 4;
+    if (a < b + bytes && b < a + bytes)
+      return set_err(G2K_EINVAL, "mix_out must not overlap mix_in");
+  }
+  if (workspace && (((uintptr_t)workspace) & 7))
+    return set_err(G2K_EINVAL, "workspace must be 8-byte aligned");
+  const int64_t need = mix_em_ws_bytes(d);
+  if (d->S > 0 && (!workspace || workspace_bytes < need))
+    return set_err(G2K_EINVAL, "workspace of %lld bytes needed (got %lld), 8-byte aligned",
+                   (long long)need, (long long)workspace_bytes);
+  if (d->S == 0) return G2K_OK;
+  return mix_em_launch(d, pred, targets, n_active, n_frames, ped_mask, mix_in, moments, resp, total,
+                       mix_out, workspace, (hipStream_t)stream);
+}
+
+int g2k_mix_sample_f32(const g2k_dims* d, const float* pred, const float* mix, uint64_t seed,
+                       float* out, int32_t* comp, void* stream) {
+  int32_t one = 1;
+  int rc = validate_nll(d, pred, mix, &one);
+  if (rc) return rc;
+  if (!out) return set_err(G2K_EINVAL, "out is NULL");
+  if ((int64_t)d->S * d->F * kL * d->Nmax == 0) return G2K_OK;
+  return mix_sample_launch(d, pred, mix, seed, out, comp, (hipStream_t)stream);
+}
+
+int64_t g2k_mix_best_of_k_workspace_bytes(const g2k_dims* d) { return sampled_ws_bytes(d, false); }
+
+int g2k_mix_best_of_k_f32(const g2k_dims* d, const float* pred, const float* targets,
+                          const int32_t* n_active, const int32_t* n_frames,
+                          const uint8_t* ped_mask, const float* mix, uint64_t seed, int32_t K,
+                          float* per_ped, float* best, float* out, void* workspace,
+                          int64_t workspace_bytes, void* stream) {
+  const int rc = validate_sampled("mix_best_of_k", kSampledMarginal, d, pred, targets, n_active, mix,
+                                  K, 0.f, out, per_ped, workspace, workspace_bytes);
+  if (rc || d->S == 0) return rc;
+  return mix_best_of_k_launch(d, pred, targets, n_active, n_frames, ped_mask, mix, seed, K, per_ped,
+                              best, out, static_cast<float*>(workspace), (hipStream_t)stream);
 }
 
 int g2k_update_f32(float* params, float* ms, const float* grad, int64_t n_params, float lr,

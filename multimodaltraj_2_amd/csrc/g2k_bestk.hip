@@ -230,4 +230,14 @@ int best_of_k_launch(bool fullcov, const g2k_dims* d, const float* pred, const f
       d, pred, targets, n_active, n_frames, ped_mask, head, seed, K, per_ped, best, out, rows, st);
 }
 
+// the Gaussian-mixture head (g2k_mix_best_of_k_f32): the same kernel with the
+// MixHead policy, mix [8][608]; geometry and workspace as the other two
+int mix_best_of_k_launch(const g2k_dims* d, const float* pred, const float* targets,
+                         const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                         const float* mix, uint64_t seed, int K, float* per_ped, float* best,
+                         float* out, float* rows, hipStream_t st) {
+  return best_of_k_launch_as<MixHead>(d, pred, targets, n_active, n_frames, ped_mask, mix, seed, K,
+                                      per_ped, best, out, rows, st);
+}
+
 }  // namespace g2k

@@ -563,6 +563,20 @@ int fullcov_stats_launch(const g2k_dims* d, const float* pred, const float* targ
 int fullcov_sample_launch(const g2k_dims* d, const float* pred, const float* chol, uint64_t seed,
                           float* out, hipStream_t st);
 
+// g2k_mix.hip (the Gaussian-mixture head, include/g2k_mix.h) and its best-of-K
+// (g2k_bestk.hip, the MixHead policy)
+int64_t mix_em_ws_bytes(const g2k_dims* d);
+int mix_em_launch(const g2k_dims* d, const float* pred, const float* targets,
+                  const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                  const float* mix_in, double* moments, double* resp, double* total, float* mix_out,
+                  void* workspace, hipStream_t st);
+int mix_sample_launch(const g2k_dims* d, const float* pred, const float* mix, uint64_t seed,
+                      float* out, int32_t* comp, hipStream_t st);
+int mix_best_of_k_launch(const g2k_dims* d, const float* pred, const float* targets,
+                         const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                         const float* mix, uint64_t seed, int K, float* per_ped, float* best,
+                         float* out, float* rows, hipStream_t st);
+
 // g2k_ops.hip
 int recur_launch(const float* A, float* h, int S, int frames, int D, int H, hipStream_t st);
 int mcr_forward_launch(const g2k_dims* d, const g2k_weights* w, const float* X, const float* Rel,

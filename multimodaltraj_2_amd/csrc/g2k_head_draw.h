@@ -148,6 +148,119 @@ struct FullCovHead {
   }
 };
 
+// ---------------------------------------------------------------------------
+// the Gaussian-mixture trajectory head (include/g2k_mix.h holds the
+// definition): mix [8][608] = per slot {w, 7 unused, b[24], L[24][24]}; a slot
+// with w == 0 is dead (nothing but its w is read)
+// ---------------------------------------------------------------------------
+constexpr int kMixSlots = 8;
+constexpr int kMixPitch = 608;                 // floats per slot of the parameter block
+constexpr int kMixOffB = 8, kMixOffL = 32;
+// A component's transposed factor in LDS.  The lanes of a wave hold different
+// components, so a column read is no longer one broadcast: with a pitch of 576
+// floats (0 mod the 64 banks) every component's column would start on the same
+// bank and the read would conflict as many ways as there are components in the
+// wave; 580 moves each component by one ds_read_b128 (4 banks), so the eight
+// components' columns start on banks 0, 4, ..., 28.
+constexpr int kMixLtPitch = kL2 * kL2 + 4;     // 580
+constexpr uint32_t kMixSelSalt = 0x9E3779B9u;
+
+// The draw is FullCovHead's with a per-lane factor: the component is selected
+// once per trajectory from step 0's key (hashed twice: 2 key + 1 and 2 key + 2
+// between them cover every 32-bit value, so one hash of any function of the
+// key would be some other element's Box-Muller input), the running sums start
+// as mu + b_m, and the steps are fullcov_advance on L_m.
+struct MixHead {
+  static constexpr const char* kPrefix = "mix_";
+  static constexpr int kJointWaveOccupancy = 2;
+  struct alignas(16) Lds {
+    float Lt[kMixSlots * kMixLtPitch];
+    float b[kMixSlots * kL2];
+    float cw[kMixSlots];
+    int live;                                  // bit m: slot m is live
+    int last;                                  // the last live slot
+  };
+  const Lds* lds;
+
+  static __device__ __forceinline__ void stage(const float* __restrict__ mix, Lds& l, int tid,
+                                               int nthreads) {
+    // every thread forms the live mask (uniform); thread 0 the cumulative weights
+    float w[kMixSlots];
+    int live = 0, last = 0;
+#pragma unroll
+    for (int m = 0; m < kMixSlots; ++m) {
+      w[m] = mix[m * kMixPitch];
+      if (w[m] != 0.f) { live |= 1 << m; last = m; }
+    }
+    if (tid == 0) {
+      double sum = 0.0;
+#pragma unroll
+      for (int m = 0; m < kMixSlots; ++m) sum += (double)w[m];
+      double c = 0.0;
+#pragma unroll
+      for (int m = 0; m < kMixSlots; ++m) {
+        c += (double)w[m] / sum;
+        l.cw[m] = m == last ? 1.f : (float)c;
+      }
+      l.live = live;
+      l.last = last;
+    }
+    for (int idx = tid; idx < kMixSlots * kL2 * kL2; idx += nthreads) {
+      const int m = idx / (kL2 * kL2), r = idx - m * (kL2 * kL2);
+      if (!((live >> m) & 1)) continue;
+      const int i = r / kL2, j = r - i * kL2;
+      float v = 0.f;
+      if (j <= i) v = mix[m * kMixPitch + kMixOffL + r];
+      l.Lt[m * kMixLtPitch + j * kL2 + i] = v;
+    }
+    for (int idx = tid; idx < kMixSlots * kL2; idx += nthreads) {
+      const int m = idx / kL2;
+      if ((live >> m) & 1) l.b[idx] = mix[m * kMixPitch + kMixOffB + (idx - m * kL2)];
+    }
+  }
+  __device__ __forceinline__ void bind(const Lds& l) { lds = &l; }
+  // the component of the trajectory whose step-0 element is e0
+  __device__ __forceinline__ int select(uint32_t lo, uint32_t hi, int64_t e0) const {
+    const uint32_t key0 = gauss_stream(lo, hi, (uint32_t)(e0 >> 32)) ^ (uint32_t)e0;
+    const uint32_t h = pcg_hash(pcg_hash(key0) + kMixSelSalt);
+    const float u = ((float)(h >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    const int live = lds->live;
+    int m = lds->last;
+#pragma unroll
+    for (int k = kMixSlots - 1; k >= 0; --k)
+      if (((live >> k) & 1) && u < lds->cw[k]) m = k;
+    return m;
+  }
+  template <class Step>
+  __device__ __forceinline__ void draw(uint32_t lo, uint32_t hi, int64_t e0, int Nmax,
+                                       const float (&mu)[kL2], Step&& step) const {
+    const uint32_t ehi0 = (uint32_t)(e0 >> 32);
+    const uint32_t stream0 = gauss_stream(lo, hi, ehi0);
+    const int m = select(lo, hi, e0);
+    const float* Lt = lds->Lt + m * kMixLtPitch;           // per lane
+    const float* bm = lds->b + m * kL2;
+    float a[kL2];
+#pragma unroll
+    for (int r = 0; r < kL2; ++r) a[r] = mu[r] + bm[r];
+    // the pins of FullCovHead::draw: step 0's element index opaque, each
+    // step's later sums formed in the step
+    uint32_t elo0 = (uint32_t)e0;
+    asm volatile("" : "+v"(elo0));
+#pragma unroll
+    for (int t = 0; t < kL; ++t) {
+      const uint32_t elo = elo0 + (uint32_t)(t * Nmax);
+      uint32_t stream = stream0;
+      if (elo < elo0) stream = gauss_stream(lo, hi, ehi0 + 1u);   // a member that straddles 2^32
+      float z0, z1;
+      gauss_normals(stream, elo, z0, z1);
+      fullcov_advance(Lt, t, z0, z1, a);
+#pragma unroll
+      for (int i = 2 * t + 2; i < kL2; ++i) asm volatile("" : "+v"(a[i]));
+      step(t, a[2 * t], a[2 * t + 1]);
+    }
+  }
+};
+
 // A pair's (a member's) 24 means and 24 target coordinates, both time-major
 // ([2t + c]: the indices are constants after unrolling, so the order is one
 // of names only); zeros for a lane that is off.

@@ -78,6 +78,8 @@ FULLCOV_JOINT_FIGURES = ("fullcov_jade", "fullcov_jfde", "fullcov_collision_rate
                          "fullcov_collision_rate_best")
 KDE_FIGURES = ("kde_nll", "kde_nll_final", "kde_clipped")
 FULLCOV_KDE_FIGURES = tuple("fullcov_" + k for k in KDE_FIGURES)
+MIX_FIGURES = ("mix_min_ade", "mix_min_fde", "mix_nll", "mix_components", "mix_weight_max",
+               "mix_loglik_gain")
 
 
 def calib_figures(hs):
@@ -109,6 +111,16 @@ def kde_figures(kd, prefix=""):
     """KDE_FIGURES (``prefix`` "fullcov_": FULLCOV_KDE_FIGURES) of a KdeNll."""
     return {prefix + "kde_nll": kd.kde_nll, prefix + "kde_nll_final": kd.kde_nll_final,
             prefix + "kde_clipped": kd.clipped_share}
+
+
+def mixture_figures(mx, bk, st, fit):
+    """MIX_FIGURES of a fitted MixtureHead: its best-of-K result and
+    MixtureStats on the evaluated scenes, and the MixtureFit that made it
+    (``mix_loglik_gain``: the last minus the first log-likelihood per pair over
+    the fit)."""
+    return dict(mix_min_ade=bk.min_ade, mix_min_fde=bk.min_fde, mix_nll=st.nll,
+                mix_components=mx.components, mix_weight_max=float(mx.weights.max().item()),
+                mix_loglik_gain=fit.gain)
 
 
 def left_out_plan(args, nmax):
@@ -165,7 +177,12 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
     from one GaussianHead.kde_nll launch (same K and seed, floor --kde_floor)
     and a log line, and with --fullcov_head FULLCOV_KDE_FIGURES from one
     FullCovHead.kde_nll launch and a log line (``keep["kde"]``,
-    ``keep["fullcov"]["kde"]``).  ``keep`` (a dict)
+    ``keep["fullcov"]["kde"]``).  --mixture_head train / eval then fits a
+    MixtureHead of --mixture_components components by --mixture_iters EM
+    iterations on the same scenes as --fullcov_head's modes (started by
+    ``MixtureHead.init_from`` a no-head full-covariance stats launch on them),
+    runs its stats and best_of_k on the left-out scenes and adds MIX_FIGURES
+    and a log line (``keep["mixture"]``).  ``keep`` (a dict)
     receives the plan, the predictions, the head and the kernels' outputs for
     a caller that checks them."""
     K = int(args.num_samples)
@@ -283,9 +300,38 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                 f"{res['kde_nll']:.6g}), final step {res['fullcov_kde_nll_final']:.6g} (per-step "
                 f"head {res['kde_nll_final']:.6g}), floor {kde_floor:g} reached by "
                 f"{res['fullcov_kde_clipped']:.4f} of the steps")
+    mx_mode = getattr(args, "mixture_head", "off") or "off"
+    mx = mx_fit = mx_st = mx_bk = None
+    if mx_mode != "off":
+        from .mixture import MixtureHead
+        mx = MixtureHead(components=int(getattr(args, "mixture_components", 3)), device=device)
+        iters = int(getattr(args, "mixture_iters", 30))
+        if mx_mode == "train":
+            fplan = fold_plan(args, params.nmax)
+            ft, fout, fone = _fused_step(args, params, fplan, device)
+            mx_fit = mx.fit(fout.pred, ft["targets"], ft["n_active"], iters=iters, n_frames=fone,
+                            ped_mask=ft["ped_mask"])
+            where = f"{fplan.S} scenes of the fold's training datasets ({mx_fit.pairs} pairs)"
+        else:
+            mx_fit = mx.fit(out.pred, t["targets"], t["n_active"], iters=iters, n_frames=one,
+                            ped_mask=t["ped_mask"])
+            where = (f"the left-out dataset itself ({mx_fit.pairs} pairs): in-sample, a bound and not "
+                     f"an estimate")
+        mx_st = mx.stats(out.pred, t["targets"], t["n_active"], n_frames=one, ped_mask=t["ped_mask"])
+        mx_bk = mx.best_of_k(out.pred, t["targets"], t["n_active"], K, seed=args.sample_seed,
+                             n_frames=one, ped_mask=t["ped_mask"], want_per_ped=False)
+        res.update(mixture_figures(mx, mx_bk, mx_st, mx_fit))
+        log(f"mixture head on dataset {args.leaveDataset}: {iters} EM iterations on {where}; "
+            f"{res['mix_components']} live components, largest weight {res['mix_weight_max']:.4f}, "
+            f"log-likelihood gained {res['mix_loglik_gain']:.6g} per pair; minADE_{K} "
+            f"{res['mix_min_ade']:.6g} minFDE_{K} {res['mix_min_fde']:.6g} (per-step head "
+            f"{res['min_ade']:.6g} / {res['min_fde']:.6g}), NLL per pair {res['mix_nll']:.6g} "
+            f"(left-out scenes)")
     if keep is not None:
         keep.update(plan=plan, pred=out.pred, head=gh.head, out=bk, n_frames=np.ones(S, np.int32),
                     joint=joint)
+        if mx is not None:
+            keep.update(mixture=dict(head=mx, fit=mx_fit, stats=mx_st, out=mx_bk))
         if calibrate:
             keep.update(calib=calib, fitted=fitted)
         if kde is not None:
