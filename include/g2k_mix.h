@@ -72,10 +72,35 @@
  *   and these draws: the same per_ped, best (draw kA, bit-identical to
  *   g2k_mix_sample_f32 at seed + kA, for pairs; pred elsewhere) and out, K in
  *   1..4096, no draw in memory, ties to the lowest k.
- * All three: S = 0 is a no-op; asynchronous, no allocation, capturable.
+ * g2k_mix_joint_eval_f32: g2k_fullcov_joint_eval_f32 (include/g2k_hip.h) with
+ *   mix in place of chol: the same outputs (per_frame_f [S, F, 4], per_frame_i
+ *   [S, F, 6] or NULL, sums_f [S, 4], sums_i [S, 6] int64; zeros where P = 0 or
+ *   f >= n_frames[s]; every element written), K in 1..4096, radius finite and
+ *   >= 0, workspace >= g2k_mix_joint_eval_workspace_bytes(d).  Draw k of a
+ *   member is bit for bit what g2k_mix_sample_f32 writes for seed (seed + k)
+ *   mod 2^64.  In joint sample k EVERY MEMBER SELECTS ITS OWN COMPONENT from
+ *   its own step-0 key: one joint sample mixes components across the
+ *   pedestrians of the scene-frame (the mixture is over a pair's residuals,
+ *   not over the scene's).
+ * g2k_mix_kde_nll_f32: g2k_fullcov_kde_nll_f32 with mix in place of chol and
+ *   these draws: the same per_ped [S, F, Nmax, 4] or NULL and out [S, 8], K in
+ *   4..4096, log_floor finite, workspace >= g2k_mix_kde_nll_workspace_bytes(d);
+ *   S = 0 or F = 0 launches nothing.  The definition is the same; the fp32
+ *   moments of the K draws are taken as a running mean and centred sums (the
+ *   draws sit around mu + b_m, not around mu), so a one-slot, b = 0 mixture
+ *   agrees with g2k_fullcov_kde_nll_f32 to rounding, not bit for bit.
+ * Both: flags, validation, workspace sizes and the S = 0 / F = 0 no-ops are
+ *   the full-covariance entry points'; no atomics, repeated calls are
+ *   bit-identical; dead slots, floats 1..7 and the entries above the diagonals
+ *   are never read.
+ * All five: S = 0 is a no-op; asynchronous, no allocation, capturable.
  * Alignment (bytes) of g2k_mix_em_f32: targets 8, moments 8, resp 8, total 8,
  * workspace 8.
  * Alignment (bytes) of g2k_mix_best_of_k_f32: targets 8, per_ped 16,
+ * workspace 4.
+ * Alignment (bytes) of g2k_mix_joint_eval_f32: targets 8, sums_i 8,
+ * workspace 4.
+ * Alignment (bytes) of g2k_mix_kde_nll_f32: targets 8, per_ped 16,
  * workspace 4.
  */
 #ifndef G2K_MIX_H_
@@ -103,6 +128,17 @@ int g2k_mix_best_of_k_f32(const g2k_dims* d, const float* pred, const float* tar
                           const uint8_t* ped_mask, const float* mix, uint64_t seed, int32_t K,
                           float* per_ped, float* best, float* out, void* workspace,
                           int64_t workspace_bytes, void* stream);
+int64_t g2k_mix_joint_eval_workspace_bytes(const g2k_dims* d);
+int g2k_mix_joint_eval_f32(const g2k_dims* d, const float* pred, const float* targets,
+                           const int32_t* n_active, const int32_t* n_frames,
+                           const uint8_t* ped_mask, const float* mix, uint64_t seed, int32_t K,
+                           float radius, float* per_frame_f, int32_t* per_frame_i, float* sums_f,
+                           int64_t* sums_i, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t g2k_mix_kde_nll_workspace_bytes(const g2k_dims* d);
+int g2k_mix_kde_nll_f32(const g2k_dims* d, const float* pred, const float* targets,
+                        const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                        const float* mix, uint64_t seed, int32_t K, float log_floor, float* per_ped,
+                        float* out, void* workspace, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -855,6 +855,35 @@ int g2k_mix_best_of_k_f32(const g2k_dims* d, const float* pred, const float* tar
                               best, out, static_cast<float*>(workspace), (hipStream_t)stream);
 }
 
+int64_t g2k_mix_joint_eval_workspace_bytes(const g2k_dims* d) { return sampled_ws_bytes(d, true); }
+
+int g2k_mix_joint_eval_f32(const g2k_dims* d, const float* pred, const float* targets,
+                           const int32_t* n_active, const int32_t* n_frames,
+                           const uint8_t* ped_mask, const float* mix, uint64_t seed, int32_t K,
+                           float radius, float* per_frame_f, int32_t* per_frame_i, float* sums_f,
+                           int64_t* sums_i, void* workspace, int64_t workspace_bytes, void* stream) {
+  const int rc = validate_sampled("mix_joint_eval", kSampledJoint, d, pred, targets, n_active, mix, K,
+                                  radius, sums_f, sums_i, workspace, workspace_bytes);
+  if (rc || d->S == 0) return rc;
+  return mix_joint_eval_launch(d, pred, targets, n_active, n_frames, ped_mask, mix, seed, K, radius,
+                               per_frame_f, per_frame_i, sums_f, sums_i,
+                               static_cast<int32_t*>(workspace), (hipStream_t)stream);
+}
+
+int64_t g2k_mix_kde_nll_workspace_bytes(const g2k_dims* d) { return g2k_kde_nll_workspace_bytes(d); }
+
+// S == 0 or F == 0 launches nothing
+int g2k_mix_kde_nll_f32(const g2k_dims* d, const float* pred, const float* targets,
+                        const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                        const float* mix, uint64_t seed, int32_t K, float log_floor, float* per_ped,
+                        float* out, void* workspace, int64_t workspace_bytes, void* stream) {
+  const int rc = validate_sampled("mix_kde_nll", kSampledKde, d, pred, targets, n_active, mix, K,
+                                  log_floor, out, per_ped, workspace, workspace_bytes);
+  if (rc || d->S == 0 || d->F == 0) return rc;
+  return mix_kde_nll_launch(d, pred, targets, n_active, n_frames, ped_mask, mix, seed, K, log_floor,
+                            per_ped, out, static_cast<float*>(workspace), (hipStream_t)stream);
+}
+
 int g2k_update_f32(float* params, float* ms, const float* grad, int64_t n_params, float lr,
                    float decay, float grad_clip, void* stream) {
   if (!params || !grad || n_params < 0 || n_params > (1 << 30))

@@ -71,7 +71,7 @@ __global__ void __launch_bounds__(kBkThreads) best_of_k_kernel(
   const int nfc = clampi(nf - f0, 0, fcn);                 // ... of them below n_frames
   const uint8_t* mask = ped_mask ? ped_mask + (size_t)s * Nmax : nullptr;
 
-  Head::stage(head_params, hlds, tid, kBkThreads);
+  Head::template stage<kBkThreads>(head_params, hlds, tid);
   // non-pairs: zeros in per_ped, pred in best
   if (per_ped || best) {
     for (int idx = tid; idx < fcn * Nmax; idx += kBkThreads) {

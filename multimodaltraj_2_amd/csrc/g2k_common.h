@@ -563,8 +563,9 @@ int fullcov_stats_launch(const g2k_dims* d, const float* pred, const float* targ
 int fullcov_sample_launch(const g2k_dims* d, const float* pred, const float* chol, uint64_t seed,
                           float* out, hipStream_t st);
 
-// g2k_mix.hip (the Gaussian-mixture head, include/g2k_mix.h) and its best-of-K
-// (g2k_bestk.hip, the MixHead policy)
+// g2k_mix.hip (the Gaussian-mixture head, include/g2k_mix.h) and its fused
+// evaluations (g2k_bestk.hip, g2k_joint.hip, g2k_kde.hip with the MixHead
+// policy; geometry and workspaces are the other heads')
 int64_t mix_em_ws_bytes(const g2k_dims* d);
 int mix_em_launch(const g2k_dims* d, const float* pred, const float* targets,
                   const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
@@ -576,6 +577,15 @@ int mix_best_of_k_launch(const g2k_dims* d, const float* pred, const float* targ
                          const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
                          const float* mix, uint64_t seed, int K, float* per_ped, float* best,
                          float* out, float* rows, hipStream_t st);
+int mix_joint_eval_launch(const g2k_dims* d, const float* pred, const float* targets,
+                          const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                          const float* mix, uint64_t seed, int K, float radius, float* per_frame_f,
+                          int32_t* per_frame_i, float* sums_f, int64_t* sums_i, int32_t* rows,
+                          hipStream_t st);
+int mix_kde_nll_launch(const g2k_dims* d, const float* pred, const float* targets,
+                       const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                       const float* mix, uint64_t seed, int K, float log_floor, float* per_ped,
+                       float* out, float* rows, hipStream_t st);
 
 // g2k_ops.hip
 int recur_launch(const float* A, float* h, int S, int frames, int D, int H, hipStream_t st);

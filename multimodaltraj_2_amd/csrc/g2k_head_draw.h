@@ -1,10 +1,11 @@
-// g2k_head_draw.h — the two probabilistic heads as device-side policies: what
-// the fused evaluations (best_of_k_kernel, g2k_bestk.hip; joint_kernel and
-// joint_wave_kernel, g2k_joint.hip) take as their template parameter.  A
-// policy owns exactly what differs between the heads:
+// g2k_head_draw.h — the probabilistic heads as device-side policies: what the
+// fused evaluations (best_of_k_kernel, g2k_bestk.hip; joint_kernel and
+// joint_wave_kernel, g2k_joint.hip; kde_nll_kernel, g2k_kde.hip) take as their
+// template parameter.  A policy owns exactly what differs between the heads:
 //   Lds                       what it keeps in LDS for the workgroup
-//   stage(p, lds, tid, n)     fills it from the head's parameters, n threads
-//                             taking part (the caller's barrier follows)
+//   stage<NT>(p, lds, tid)    fills it from the head's parameters, NT threads
+//                             taking part, a compile-time constant (the
+//                             caller's barrier follows)
 //   bind(lds)                 what a lane then draws from
 //   draw(lo, hi, e0, Nmax, mu, step)
 //                             one draw of one member for seed (hi, lo), whose
@@ -14,6 +15,11 @@
 //   kPrefix                   the head's prefix in a launcher's messages
 //   kJointWaveOccupancy       joint_wave_kernel's amdgpu_waves_per_eu (1: no
 //                             hint, the compiler's default)
+//   kKdeRunningMean           kde_nll_kernel's moments (g2k_kde.hip): false =
+//                             plain sums of d = x - mu (the draws sit around
+//                             the means), true = a running mean and centred
+//                             sums (the draws sit around mu + b_m, |b_m| far
+//                             above the spread)
 // Each draw is the code of its head's sampler (gauss_draw, g2k_common.h, and
 // g2k_gauss_sample_kernel; fullcov_advance below and g2k_fullcov_sample_kernel),
 // so that a draw made inside a fused evaluation is, bit for bit, the sampler's.
@@ -29,12 +35,13 @@ namespace {
 struct PerStepHead {
   static constexpr const char* kPrefix = "";
   static constexpr int kJointWaveOccupancy = 1;
+  static constexpr bool kKdeRunningMean = false;
   struct Lds { float4 hs[kL]; };       // per step {sigma_x, sigma_y, rho, sqrt(1 - rho^2)}
   GaussStep gs[kL];                    // wave-uniform: scalar registers
 
-  static __device__ __forceinline__ void stage(const float* __restrict__ head, Lds& lds, int tid,
-                                               int nthreads) {
-    for (int t = tid; t < kL; t += nthreads) {
+  template <int NT>
+  static __device__ __forceinline__ void stage(const float* __restrict__ head, Lds& lds, int tid) {
+    for (int t = tid; t < kL; t += NT) {
       const GaussStep g = gauss_step(head, t);
       lds.hs[t] = make_float4(g.sx, g.sy, g.rho, g.sq);
     }
@@ -106,12 +113,13 @@ __device__ __forceinline__ void fullcov_advance(const float* Lt, int t, float z0
 struct FullCovHead {
   static constexpr const char* kPrefix = "fullcov_";
   static constexpr int kJointWaveOccupancy = 2;
+  static constexpr bool kKdeRunningMean = false;
   struct alignas(16) Lds { float Lt[kL2 * kL2]; };
   const float* Lt;
 
-  static __device__ __forceinline__ void stage(const float* __restrict__ chol, Lds& lds, int tid,
-                                               int nthreads) {
-    fullcov_load_lt(chol, lds.Lt, tid, nthreads);
+  template <int NT>
+  static __device__ __forceinline__ void stage(const float* __restrict__ chol, Lds& lds, int tid) {
+    fullcov_load_lt(chol, lds.Lt, tid, NT);
   }
   __device__ __forceinline__ void bind(const Lds& lds) { Lt = lds.Lt; }
   template <class Step>
@@ -173,6 +181,7 @@ constexpr uint32_t kMixSelSalt = 0x9E3779B9u;
 struct MixHead {
   static constexpr const char* kPrefix = "mix_";
   static constexpr int kJointWaveOccupancy = 2;
+  static constexpr bool kKdeRunningMean = true;
   struct alignas(16) Lds {
     float Lt[kMixSlots * kMixLtPitch];
     float b[kMixSlots * kL2];
@@ -182,8 +191,11 @@ struct MixHead {
   };
   const Lds* lds;
 
-  static __device__ __forceinline__ void stage(const float* __restrict__ mix, Lds& l, int tid,
-                                               int nthreads) {
+  template <int NT>
+  static __device__ __forceinline__ void stage(const float* __restrict__ mix, Lds& l, int tid) {
+    // a thread takes at most kTrips entries of a factor, in registers: NT is a
+    // constant so that the trips past a factor's end fold away
+    static_assert(NT >= 64 && NT % 64 == 0, "MixHead::stage: whole waves, at least one");
     // every thread forms the live mask (uniform); thread 0 the cumulative weights
     float w[kMixSlots];
     int live = 0, last = 0;
@@ -205,15 +217,36 @@ struct MixHead {
       l.live = live;
       l.last = last;
     }
-    for (int idx = tid; idx < kMixSlots * kL2 * kL2; idx += nthreads) {
-      const int m = idx / (kL2 * kL2), r = idx - m * (kL2 * kL2);
+    // The live slots' factors, a slot's 576 entries strided over the threads
+    // (NT >= 64: at most kTrips each).  Every load of every live slot
+    // is issued before the first store (the slot test is uniform), so a
+    // one-wave workgroup pays one round trip to memory and not one per trip:
+    // joint_wave_kernel's units are short, their staging is a large part of
+    // them.
+    constexpr int kTrips = (kL2 * kL2 + 63) / 64;          // 9
+    float v[kMixSlots][kTrips];
+#pragma unroll
+    for (int m = 0; m < kMixSlots; ++m) {
       if (!((live >> m) & 1)) continue;
-      const int i = r / kL2, j = r - i * kL2;
-      float v = 0.f;
-      if (j <= i) v = mix[m * kMixPitch + kMixOffL + r];
-      l.Lt[m * kMixLtPitch + j * kL2 + i] = v;
+#pragma unroll
+      for (int q = 0; q < kTrips; ++q) {
+        const int r = q * NT + tid;
+        const int i = r / kL2, j = r - i * kL2;
+        v[m][q] = 0.f;
+        if (r < kL2 * kL2 && j <= i) v[m][q] = mix[m * kMixPitch + kMixOffL + r];
+      }
     }
-    for (int idx = tid; idx < kMixSlots * kL2; idx += nthreads) {
+#pragma unroll
+    for (int m = 0; m < kMixSlots; ++m) {
+      if (!((live >> m) & 1)) continue;
+#pragma unroll
+      for (int q = 0; q < kTrips; ++q) {
+        const int r = q * NT + tid;
+        const int i = r / kL2, j = r - i * kL2;
+        if (r < kL2 * kL2) l.Lt[m * kMixLtPitch + j * kL2 + i] = v[m][q];
+      }
+    }
+    for (int idx = tid; idx < kMixSlots * kL2; idx += NT) {
       const int m = idx / kL2;
       if ((live >> m) & 1) l.b[idx] = mix[m * kMixPitch + kMixOffB + (idx - m * kL2)];
     }

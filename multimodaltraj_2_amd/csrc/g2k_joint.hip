@@ -2,12 +2,14 @@
 // JADE_K / JFDE_K (one draw index for the whole scene-frame) and the collision
 // counts of the draws, of the mean prediction and of the targets.  ONE pair of
 // kernels, joint_kernel<Head> and joint_wave_kernel<Head>, instantiated for
-// the per-step bivariate-Gaussian head (g2k_joint_eval_f32) and for the
-// full-covariance trajectory head (g2k_fullcov_joint_eval_f32); the heads are
-// the policies of g2k_head_draw.h.  The build's: the reference has no
+// the per-step bivariate-Gaussian head (g2k_joint_eval_f32), for the
+// full-covariance trajectory head (g2k_fullcov_joint_eval_f32) and for the
+// Gaussian-mixture head (g2k_mix_joint_eval_f32, include/g2k_mix.h); the heads
+// are the policies of g2k_head_draw.h.  The build's: the reference has no
 // probabilistic head, so PARITY UNPINNED; tests/joint_ref.py restates the
 // definition over oracle/g2k_ref.py gauss_sample and tests/bestk_ref.py,
-// tests/fullcov_joint_ref.py over tests/fullcov_ref.py.
+// tests/fullcov_joint_ref.py over tests/fullcov_ref.py, tests/mix_eval_ref.py
+// over tests/mixture_ref.py.
 //
 // Definition.  Inputs as g2k_best_of_k_f32 (g2k_bestk.hip) plus radius
 // (finite, >= 0).  The MEMBERS of scene-frame (s, f), f < n_frames[s], are the
@@ -196,7 +198,7 @@ __global__ void __launch_bounds__(kJtWaves * 64) joint_kernel(
   const int nf = n_frames ? clampi(n_frames[s], 0, F) : F;
   int32_t* row = rows + (size_t)blockIdx.x * kJtRow;
 
-  Head::stage(head_params, hlds, tid, CAP);
+  Head::template stage<CAP>(head_params, hlds, tid);
   // compact the members: thread i owns member i = column midx[i]
   bool mem = f < nf && tid < nact;
   if (mem && ped_mask) mem = ped_mask[(size_t)s * Nmax + tid] != 0;
@@ -294,8 +296,10 @@ __global__ void __launch_bounds__(kJtWaves * 64) joint_kernel(
 // start 16 bytes off a multiple of the bank cycle, so their reads do not
 // collide), sums run over the group's lanes by an xor butterfly.  The groups'
 // results are merged like the units' (lexicographic minima, integer sums).  The
-// groups draw different k from the same head: what they read of it in LDS is
-// the same address in every lane.  The occupancy hint is the head's
+// groups draw different k from the same head: what the per-step and the
+// full-covariance head read of it in LDS is the same address in every lane
+// (the mixture head's lanes read their own component's factor, whatever the
+// group: MixHead, g2k_head_draw.h).  The occupancy hint is the head's
 // (kJointWaveOccupancy): without it the allocator settles the full-covariance
 // instantiation at 256 VGPRs + 1 AGPR, one register over two waves per SIMD;
 // with it 256 + 0, scratch 0, nothing spilled.  The per-step instantiation
@@ -318,7 +322,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Head::k
   const int nf = n_frames ? clampi(n_frames[s], 0, F) : F;
   int32_t* row = rows + (size_t)blockIdx.x * kJtRow;
 
-  Head::stage(head_params, hlds, lane, 64);
+  Head::template stage<64>(head_params, hlds, lane);
   bool mem = f < nf && lane < nact;                        // Nmax <= 64: lane n looks at column n
   if (mem && ped_mask) mem = ped_mask[(size_t)s * Nmax + lane] != 0;
   const unsigned long long bal = __ballot(mem);
@@ -512,6 +516,22 @@ int joint_eval_launch(bool fullcov, const g2k_dims* d, const float* pred, const 
   return (fullcov ? joint_eval_launch_as<FullCovHead> : joint_eval_launch_as<PerStepHead>)(
       d, pred, targets, n_active, n_frames, ped_mask, head, seed, K, radius, per_frame_f, per_frame_i,
       sums_f, sums_i, rows, st);
+}
+
+// the Gaussian-mixture head (g2k_mix_joint_eval_f32): the same kernels with
+// the MixHead policy, mix [8][608]; geometry and workspace as the other two.
+// Every member selects its own component, so one joint sample mixes components
+// across the members of a scene-frame.  joint_kernel<MixHead> holds 69.7 KB of
+// static LDS (the double-buffered sample, 48 KB, beside the eight staged
+// factors): above 64 KB, inside gfx950's 160 KB per workgroup, two workgroups
+// per CU.
+int mix_joint_eval_launch(const g2k_dims* d, const float* pred, const float* targets,
+                          const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                          const float* mix, uint64_t seed, int K, float radius, float* per_frame_f,
+                          int32_t* per_frame_i, float* sums_f, int64_t* sums_i, int32_t* rows,
+                          hipStream_t st) {
+  return joint_eval_launch_as<MixHead>(d, pred, targets, n_active, n_frames, ped_mask, mix, seed, K,
+                                       radius, per_frame_f, per_frame_i, sums_f, sums_i, rows, st);
 }
 
 }  // namespace g2k

@@ -1,10 +1,11 @@
 // g2k_kde.hip — fused KDE-NLL evaluation of a probabilistic head's samples
 // (the KDE-NLL of Trajectron++): ONE kernel, kde_nll_kernel<Head>, instantiated
-// for the per-step bivariate-Gaussian head (g2k_kde_nll_f32) and for the
-// full-covariance trajectory head (g2k_fullcov_kde_nll_f32); the heads are the
-// policies of g2k_head_draw.h.  The build's: the reference has no probabilistic
-// head, so PARITY UNPINNED; pinned against scipy.stats.gaussian_kde through
-// tests/kde_ref.py.
+// for the per-step bivariate-Gaussian head (g2k_kde_nll_f32), for the
+// full-covariance trajectory head (g2k_fullcov_kde_nll_f32) and for the
+// Gaussian-mixture head (g2k_mix_kde_nll_f32, include/g2k_mix.h); the heads are
+// the policies of g2k_head_draw.h.  The build's: the reference has no
+// probabilistic head, so PARITY UNPINNED; pinned against
+// scipy.stats.gaussian_kde through tests/kde_ref.py.
 //
 // Definition.  Inputs and pairs as g2k_best_of_k_f32 (g2k_bestk.hip), K in
 // [4, 4096], log_floor finite.  Draw k = what the head's sampler writes for
@@ -29,7 +30,13 @@
 // targets in registers, time-major.  Two passes over the same K draws, none
 // stored: the second pass makes the draws again from the counter.
 //   pass 0   per step the five moments of d = x - mu (sum dx, dy, dx^2, dy^2,
-//            dx dy; fp32; centred on the mean so that the sums stay small)
+//            dx dy; fp32; centred on the mean so that the sums stay small).
+//            The mixture head (Head::kKdeRunningMean; g2k_mix_kde_nll_f32)
+//            draws around mu + b_m with |b_m| many times the spread, where
+//            sum d^2 - (sum d)^2 / K cancels in fp32: its lanes keep a running
+//            mean of d and the sums of the centred products (Welford's update),
+//            and the butterfly merges them by Chan's formula; the covariance
+//            is then the centred sum / (K - 1) with nothing subtracted
 //   combine  the KS lanes' moments by a butterfly (every lane of the group ends
 //            with the same bits), then per step IN DOUBLE: covariance, Scott's
 //            factor, determinant, inverse and the constant -log K - log 2 pi -
@@ -75,7 +82,7 @@ __global__ void __launch_bounds__(kBkThreads) kde_nll_kernel(
   const int nfc = clampi(nf - f0, 0, fcn);                 // ... of them below n_frames
   const uint8_t* mask = ped_mask ? ped_mask + (size_t)s * Nmax : nullptr;
 
-  Head::stage(head_params, hlds, tid, kBkThreads);
+  Head::template stage<kBkThreads>(head_params, hlds, tid);
   // non-pairs: zeros in per_ped
   if (per_ped) {
     for (int idx = tid; idx < fcn * Nmax; idx += kBkThreads) {
@@ -112,20 +119,37 @@ __global__ void __launch_bounds__(kBkThreads) kde_nll_kernel(
       for (int i = 0; i < 6; ++i) w[t][i] = 0.f;
     }
     const int kend = on ? K : 0;
+    float cnt = 0.f;                                       // kKdeRunningMean: this lane's draws so far
 #pragma nounroll
     for (int pass = 0; pass < 2; ++pass) {
 #pragma nounroll
       for (int k = j; k < kend; k += KS) {
         const uint32_t lo = seed_lo + (uint32_t)k;         // (seed + k) mod 2^64
         const uint32_t hi = seed_hi + (lo < seed_lo ? 1u : 0u);
+        float rc = 0.f;
+        if constexpr (Head::kKdeRunningMean) {
+          if (!pass) { cnt += 1.f; rc = 1.0f / cnt; }
+        }
         head.draw(lo, hi, e0, Nmax, mu, [&](int t, float x, float y) {
           if (!pass) {
             const float dx = x - mu[2 * t], dy = y - mu[2 * t + 1];
-            w[t][0] += dx;
-            w[t][1] += dy;
-            w[t][2] = fmaf(dx, dx, w[t][2]);
-            w[t][3] = fmaf(dy, dy, w[t][3]);
-            w[t][4] = fmaf(dx, dy, w[t][4]);
+            if constexpr (Head::kKdeRunningMean) {
+              // {mean dx, mean dy, sum of centred dx^2, dy^2, dx dy} of the
+              // lane's draws so far (Welford's update)
+              const float ux = dx - w[t][0], uy = dy - w[t][1];
+              w[t][0] = fmaf(ux, rc, w[t][0]);
+              w[t][1] = fmaf(uy, rc, w[t][1]);
+              const float vx = dx - w[t][0], vy = dy - w[t][1];
+              w[t][2] = fmaf(ux, vx, w[t][2]);
+              w[t][3] = fmaf(uy, vy, w[t][3]);
+              w[t][4] = fmaf(ux, vy, w[t][4]);
+            } else {
+              w[t][0] += dx;
+              w[t][1] += dy;
+              w[t][2] = fmaf(dx, dx, w[t][2]);
+              w[t][3] = fmaf(dy, dy, w[t][3]);
+              w[t][4] = fmaf(dx, dy, w[t][4]);
+            }
           } else {
             const float ex = tg[2 * t] - x, ey = tg[2 * t + 1] - y;
             const float q = fmaf(ex, fmaf(w[t][0], ex, 2.f * w[t][2] * ey), w[t][1] * ey * ey);
@@ -140,10 +164,39 @@ __global__ void __launch_bounds__(kBkThreads) kde_nll_kernel(
       if (pass) break;
       // the group's moments, the same bits in each of its lanes
       for (int off = 1; off < KS; off <<= 1) {             // every lane takes part
+        if constexpr (Head::kKdeRunningMean) {
+          // Chan's merge of two lanes' (count, means, centred sums); A is the
+          // lane whose bit `off` is clear, in both lanes of the exchange, so
+          // that both form the same bits.  A lane without a draw has count 0
+          // and zeros: the other lane's values pass through unchanged.
+          const float ocnt = __shfl_xor(cnt, off);
+          const bool low = !(tid & off);
+          const float nA = low ? cnt : ocnt, nB = low ? ocnt : cnt;
+          cnt = nA + nB;
+          const float fB = cnt > 0.f ? nB / cnt : 0.f;     // nB / n
+          const float fAB = nA * fB;                       // nA nB / n
 #pragma unroll
-        for (int t = 0; t < kL; ++t) {
+          for (int t = 0; t < kL; ++t) {
+            float A[5], B[5];
 #pragma unroll
-          for (int i = 0; i < 5; ++i) w[t][i] += __shfl_xor(w[t][i], off);
+            for (int i = 0; i < 5; ++i) {
+              const float o = __shfl_xor(w[t][i], off);
+              A[i] = low ? w[t][i] : o;
+              B[i] = low ? o : w[t][i];
+            }
+            const float ex = B[0] - A[0], ey = B[1] - A[1];
+            w[t][0] = fmaf(ex, fB, A[0]);
+            w[t][1] = fmaf(ey, fB, A[1]);
+            w[t][2] = fmaf(ex * ex, fAB, A[2] + B[2]);
+            w[t][3] = fmaf(ey * ey, fAB, A[3] + B[3]);
+            w[t][4] = fmaf(ex * ey, fAB, A[4] + B[4]);
+          }
+        } else {
+#pragma unroll
+          for (int t = 0; t < kL; ++t) {
+#pragma unroll
+            for (int i = 0; i < 5; ++i) w[t][i] += __shfl_xor(w[t][i], off);
+          }
         }
       }
       // the bandwidth, in double; its registers take the moments' place
@@ -151,9 +204,10 @@ __global__ void __launch_bounds__(kBkThreads) kde_nll_kernel(
       for (int t = 0; t < kL; ++t) {
         const double sx = w[t][0], sy = w[t][1];
         const double rk = 1.0 / (double)K, rk1 = scott / (double)(K - 1);
-        const double hxx = ((double)w[t][2] - sx * sx * rk) * rk1;
-        const double hyy = ((double)w[t][3] - sy * sy * rk) * rk1;
-        const double hxy = ((double)w[t][4] - sx * sy * rk) * rk1;
+        // kKdeRunningMean: the sums are centred already
+        const double hxx = ((double)w[t][2] - (Head::kKdeRunningMean ? 0.0 : sx * sx * rk)) * rk1;
+        const double hyy = ((double)w[t][3] - (Head::kKdeRunningMean ? 0.0 : sy * sy * rk)) * rk1;
+        const double hxy = ((double)w[t][4] - (Head::kKdeRunningMean ? 0.0 : sx * sy * rk)) * rk1;
         const double det = hxx * hyy - hxy * hxy;
         const bool ok = det > 0.0 && det < __builtin_inf();
         const double rdet = 1.0 / (ok ? det : 1.0);
@@ -262,6 +316,17 @@ int kde_nll_launch(bool fullcov, const g2k_dims* d, const float* pred, const flo
                    float* rows, hipStream_t st) {
   return (fullcov ? kde_nll_launch_as<FullCovHead> : kde_nll_launch_as<PerStepHead>)(
       d, pred, targets, n_active, n_frames, ped_mask, head, seed, K, log_floor, per_ped, out, rows, st);
+}
+
+// the Gaussian-mixture head (g2k_mix_kde_nll_f32): the same kernel with the
+// MixHead policy, mix [8][608], and the running-mean moments; geometry and
+// workspace as the other two
+int mix_kde_nll_launch(const g2k_dims* d, const float* pred, const float* targets,
+                       const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                       const float* mix, uint64_t seed, int K, float log_floor, float* per_ped,
+                       float* out, float* rows, hipStream_t st) {
+  return kde_nll_launch_as<MixHead>(d, pred, targets, n_active, n_frames, ped_mask, mix, seed, K,
+                                    log_floor, per_ped, out, rows, st);
 }
 
 }  // namespace g2k

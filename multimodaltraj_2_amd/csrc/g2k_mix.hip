@@ -457,7 +457,7 @@ __global__ void __launch_bounds__(256) g2k_mix_sample_kernel(
     const float* __restrict__ pred, const float* __restrict__ mix, int64_t slots, int Nmax,
     uint32_t seed_lo, uint32_t seed_hi, float* __restrict__ out, int32_t* __restrict__ comp) {
   __shared__ MixHead::Lds hlds;
-  MixHead::stage(mix, hlds, threadIdx.x, 256);
+  MixHead::stage<256>(mix, hlds, threadIdx.x);
   __syncthreads();
   MixHead head;
   head.bind(hlds);

@@ -80,6 +80,8 @@ KDE_FIGURES = ("kde_nll", "kde_nll_final", "kde_clipped")
 FULLCOV_KDE_FIGURES = tuple("fullcov_" + k for k in KDE_FIGURES)
 MIX_FIGURES = ("mix_min_ade", "mix_min_fde", "mix_nll", "mix_components", "mix_weight_max",
                "mix_loglik_gain")
+MIX_JOINT_FIGURES = ("mix_jade", "mix_jfde", "mix_collision_rate", "mix_collision_rate_best")
+MIX_KDE_FIGURES = tuple("mix_" + k for k in KDE_FIGURES)
 
 
 def calib_figures(hs):
@@ -107,8 +109,15 @@ def fullcov_joint_figures(je):
                 fullcov_collision_rate_best=je.collision_rate_best)
 
 
+def mixture_joint_figures(je):
+    """MIX_JOINT_FIGURES of a MixtureHead.joint_eval result."""
+    return dict(mix_jade=je.jade, mix_jfde=je.jfde, mix_collision_rate=je.collision_rate,
+                mix_collision_rate_best=je.collision_rate_best)
+
+
 def kde_figures(kd, prefix=""):
-    """KDE_FIGURES (``prefix`` "fullcov_": FULLCOV_KDE_FIGURES) of a KdeNll."""
+    """KDE_FIGURES (``prefix`` "fullcov_": FULLCOV_KDE_FIGURES, "mix_":
+    MIX_KDE_FIGURES) of a KdeNll."""
     return {prefix + "kde_nll": kd.kde_nll, prefix + "kde_nll_final": kd.kde_nll_final,
             prefix + "kde_clipped": kd.clipped_share}
 
@@ -182,7 +191,12 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
     iterations on the same scenes as --fullcov_head's modes (started by
     ``MixtureHead.init_from`` a no-head full-covariance stats launch on them),
     runs its stats and best_of_k on the left-out scenes and adds MIX_FIGURES
-    and a log line (``keep["mixture"]``).  ``keep`` (a dict)
+    and a log line (``keep["mixture"]``); with --collision_radius R > 0 also
+    MIX_JOINT_FIGURES from one MixtureHead.joint_eval launch and with
+    --kde_nll 1 MIX_KDE_FIGURES from one MixtureHead.kde_nll launch, a log
+    line each, after the mixture's line and with the other heads' K, seed,
+    radius and floor (``keep["mixture"]["joint"]``, ``keep["mixture"]["kde"]``).
+    ``keep`` (a dict)
     receives the plan, the predictions, the head and the kernels' outputs for
     a caller that checks them."""
     K = int(args.num_samples)
@@ -301,7 +315,7 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                 f"head {res['kde_nll_final']:.6g}), floor {kde_floor:g} reached by "
                 f"{res['fullcov_kde_clipped']:.4f} of the steps")
     mx_mode = getattr(args, "mixture_head", "off") or "off"
-    mx = mx_fit = mx_st = mx_bk = None
+    mx = mx_fit = mx_st = mx_bk = mx_joint = mx_kde = None
     if mx_mode != "off":
         from .mixture import MixtureHead
         mx = MixtureHead(components=int(getattr(args, "mixture_components", 3)), device=device)
@@ -327,11 +341,36 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
             f"{res['mix_min_ade']:.6g} minFDE_{K} {res['mix_min_fde']:.6g} (per-step head "
             f"{res['min_ade']:.6g} / {res['min_fde']:.6g}), NLL per pair {res['mix_nll']:.6g} "
             f"(left-out scenes)")
+        if radius > 0:
+            mx_joint = mx.joint_eval(out.pred, t["targets"], t["n_active"], K, radius,
+                                     seed=args.sample_seed, n_frames=one, ped_mask=t["ped_mask"],
+                                     want_per_frame=keep is not None)
+            res.update(mixture_joint_figures(mx_joint))
+            log(f"mixture joint best-of-K on dataset {args.leaveDataset}: radius {radius:g}, "
+                f"K {K}, JADE_{K} {res['mix_jade']:.6g} JFDE_{K} {res['mix_jfde']:.6g} "
+                f"(per-step head {res['jade']:.6g} / {res['jfde']:.6g}), collision rate: samples "
+                f"{res['mix_collision_rate']:.6g} (per-step head {res['collision_rate']:.6g}) "
+                f"best joint sample {res['mix_collision_rate_best']:.6g} (per-step head "
+                f"{res['collision_rate_best']:.6g})")
+        if want_kde:
+            mx_kde = mx.kde_nll(out.pred, t["targets"], t["n_active"], K, seed=args.sample_seed,
+                                log_floor=kde_floor, n_frames=one, ped_mask=t["ped_mask"],
+                                want_per_ped=keep is not None)
+            res.update(kde_figures(mx_kde, "mix_"))
+            log(f"mixture KDE-NLL of the {K} draws on dataset {args.leaveDataset}: "
+                f"{res['mix_kde_nll']:.6g} per pair and step (per-step head "
+                f"{res['kde_nll']:.6g}), final step {res['mix_kde_nll_final']:.6g} (per-step "
+                f"head {res['kde_nll_final']:.6g}), floor {kde_floor:g} reached by "
+                f"{res['mix_kde_clipped']:.4f} of the steps")
     if keep is not None:
         keep.update(plan=plan, pred=out.pred, head=gh.head, out=bk, n_frames=np.ones(S, np.int32),
                     joint=joint)
         if mx is not None:
             keep.update(mixture=dict(head=mx, fit=mx_fit, stats=mx_st, out=mx_bk))
+            if mx_joint is not None:
+                keep["mixture"]["joint"] = mx_joint
+            if mx_kde is not None:
+                keep["mixture"]["kde"] = mx_kde
         if calibrate:
             keep.update(calib=calib, fitted=fitted)
         if kde is not None:

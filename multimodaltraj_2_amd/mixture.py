@@ -11,7 +11,9 @@ its parity is unpinned (tests/mixture_ref.py is the float64 checker).
 a host read in between, ``stats`` the E-step alone (the NLL of a given
 mixture), ``sample`` one reproducible draw per (scene, frame, pedestrian) and
 ``best_of_k`` the fused minADE_K / minFDE_K over such draws
-(csrc/g2k_bestk.hip with the MixHead policy).
+(csrc/g2k_bestk.hip with the MixHead policy); ``joint_eval`` and ``kde_nll``
+are the other heads' fused joint best-of-K and KDE-NLL over the same draws
+(csrc/g2k_joint.hip, csrc/g2k_kde.hip).
 
 The entry points were added after ABI 11 and are declared in a header of their
 own, so this module binds them itself on the handle ``_lib.load()`` returns
@@ -27,7 +29,7 @@ import torch
 
 from . import _lib
 from .frame_step import OBS_LEN, PRED_LEN, _check_dev, _ptr, _stream
-from .nll import _best_of_k, _check_pairs_inputs
+from .nll import _best_of_k, _check_pairs_inputs, _joint_eval, _kde_nll
 
 DIM = 2 * PRED_LEN
 SLOTS = 8
@@ -44,6 +46,13 @@ SYMBOLS = {
     "g2k_mix_best_of_k_workspace_bytes": (_i64, [_D]),
     "g2k_mix_best_of_k_f32": (_int, [_D, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64,
                                      ctypes.c_int32, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "g2k_mix_joint_eval_workspace_bytes": (_i64, [_D]),
+    "g2k_mix_joint_eval_f32": (_int, [_D, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64,
+                                      ctypes.c_int32, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _i64,
+                                      _vp]),
+    "g2k_mix_kde_nll_workspace_bytes": (_i64, [_D]),
+    "g2k_mix_kde_nll_f32": (_int, [_D, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64,
+                                   ctypes.c_int32, ctypes.c_float, _vp, _vp, _vp, _i64, _vp]),
 }
 
 
@@ -331,3 +340,28 @@ class MixtureHead:
         self._check_params(pred.device)
         return _best_of_k("g2k_mix_best_of_k_f32", self.params, d, pred, targets, n_active, k, seed,
                           n_frames, ped_mask, want_per_ped, want_best, stream)
+
+    def kde_nll(self, pred, targets, n_active, k, seed=0, *, log_floor=-20.0, n_frames=None,
+                ped_mask=None, want_per_ped=False, targets_shared=False, stream=None):
+        """KDE-NLL in one launch (g2k_mix_kde_nll_f32): FullCovHead.kde_nll over
+        this head's draws ``sample(pred, seed + i)``, i < k -> nll.KdeNll."""
+        load()
+        d = self._dims(pred)
+        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
+        self._check_params(pred.device)
+        return _kde_nll("g2k_mix_kde_nll_f32", self.params, d, pred, targets, n_active, k, seed,
+                        log_floor, n_frames, ped_mask, want_per_ped, stream)
+
+    def joint_eval(self, pred, targets, n_active, k, radius, seed=0, *, n_frames=None, ped_mask=None,
+                   targets_shared=False, want_per_frame=True, stream=None):
+        """Joint best-of-K evaluation in one launch (g2k_mix_joint_eval_f32):
+        FullCovHead.joint_eval over this head's draws; draw i < k of EVERY
+        member of a scene-frame is ``sample(pred, seed + i)``, each member with
+        the component its own selector picks, so one joint sample mixes
+        components across the pedestrians -> nll.JointEval."""
+        load()
+        d = self._dims(pred)
+        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
+        self._check_params(pred.device)
+        return _joint_eval("g2k_mix_joint_eval_f32", self.params, d, pred, targets, n_active, k,
+                           radius, seed, n_frames, ped_mask, want_per_frame, stream, gpu_only=True)
