@@ -4,7 +4,7 @@ the build's own: --data_root (Q8), --device, --mode,
 --log_dir, --save_dir, --seed, --use_grid_lstm, --loss, --num_samples,
 --sample_seed, --head_log_sigma, --collision_radius, --fit_head,
 --calibration, --fullcov_head, --mixture_head, --mixture_components,
---mixture_iters, --kde_nll, --kde_floor."""
+--mixture_iters, --kde_nll, --kde_floor, --sample_scores."""
 import argparse
 
 
@@ -100,6 +100,11 @@ class ArgsParser:
                              'full-covariance head')
     parser.add_argument('--kde_floor', type=float, default=-20.0,
                         help='--kde_nll: the floor of a step\'s log density')
+    parser.add_argument('--sample_scores', type=int, choices=(0, 1), default=0,
+                        help='--num_samples K (2 <= K <= 256): 1 also reports the energy scores '
+                             '(24-D norm, ADE, FDE), the expected ADE / FDE of a draw, the average '
+                             'pairwise displacement and the variogram score of the K draws, of the '
+                             'per-step head and, with --fullcov_head / --mixture_head, of those heads')
     parser.add_argument('--train_scenes', type=int, default=0,
                         help='--mode train: distinct scenes used (0: all of the fold)')
     parser.add_argument('--valid_from_seed', type=int, default=0,

@@ -16,7 +16,8 @@ CSRC = os.path.join(HERE, "csrc")
 SRC = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
 CXX_SRC = sorted(glob.glob(os.path.join(CSRC, "*.cpp")))   # host-only C++ (g++)
 HDR = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(ROOT, "include", "g2k_hip.h"),
-                                                      os.path.join(ROOT, "include", "g2k_mix.h")]
+                                                      os.path.join(ROOT, "include", "g2k_mix.h"),
+                                                      os.path.join(ROOT, "include", "g2k_scores.h")]
 OUT = os.path.join(HERE, "libg2k_hip.so")
 OBJ = os.path.join(HERE, "build")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

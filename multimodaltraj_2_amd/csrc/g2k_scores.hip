@@ -1,0 +1,407 @@
+// g2k_scores.hip — fused trajectory-level scores of a probabilistic head's
+// samples: the energy score's two terms (with the ADE, the FDE and the 24-D
+// norm), the APD and the variogram score of order 1/2.  ONE kernel,
+// sample_scores_kernel<Head>, instantiated for the per-step head
+// (g2k_sample_scores_f32), the full-covariance head
+// (g2k_fullcov_sample_scores_f32) and the mixture head
+// (g2k_mix_sample_scores_f32); the heads are the policies of g2k_head_draw.h.
+// The C entry points are at the end of this file, declared in
+// include/g2k_scores.h (added after ABI 11: bound by symbol).  The build's: the
+// reference has no probabilistic head, so PARITY UNPINNED; pinned against
+// tests/scores_ref.py.
+//
+// Definition.  Inputs and pairs as g2k_best_of_k_f32 (g2k_bestk.hip), K in
+// [2, 256].  Draw k = what the head's sampler writes for seed (seed + k) mod
+// 2^64.  X_k(t) draw k's position at step t, Y(t) the target; for two
+// trajectories A, B:
+//   a(A, B) = 1/12 sum_t ||A(t) - B(t)||    f(A, B) = ||A(11) - B(11)||
+//   r(A, B) = ||A - B|| over the 24 coordinates
+// per_ped [S, F, Nmax, 8] (or NULL), per pair:
+//   0..2  mA, mF, mR = 1/K sum_k {a, f, r}(X_k, Y)
+//   3..5  pA, pF, pR = 2/(K (K - 1)) sum_{k<l} {a, f, r}(X_k, X_l)
+//   6     vs = sum_{t<u} (||Y(t) - Y(u)||^(1/2) - 1/K sum_k ||X_k(t) - X_k(u)||^(1/2))^2
+//   7     0
+// zeros for non-pairs, every element written; out [S, 8] = the sums of columns
+// 0..6 over the scene's pairs and the pair count, fixed summation order, no
+// atomics.  The host forms es_traj = mR - pR / 2 (the fair energy score of the
+// 24-D law), es_ade = mA - pA / 2, es_fde = mF - pF / 2.
+//
+// Geometry (scores_geom below).  Unlike best-of-K and the KDE-NLL, the K draws
+// of a pair must all be live at once: every couple of them is compared.  A
+// draw is made ONCE and kept in LDS, xy[slot][24] (time-major, 96 B; a pitch of
+// 28 floats, which spreads the 16 lanes of a ds_read_b128 group over 16
+// different bank quads where 24 collides two ways, measured the same to within
+// 1 %: DESIGN.md §6j — the walk is not bound by LDS reads).  One
+// workgroup of 256 threads per (scene, chunk of FC frames); a pass takes G =
+// min(256 / K, 32) pairs, lane tid owns (pair tid / K, draw tid % K) and LDS
+// slot tid.  Per pass, three barriers:
+//   draw     the lane draws X_k into registers, takes a, f, r against the
+//            target and stores X_k in its slot
+//   couples  the lane walks the partners l = k + 1, ..., k + h (mod K) from
+//            LDS, 6 ds_read_b128 each, h = (K - 1) / 2, one more for the lanes
+//            k < K / 2 of an even K (the antipodal couple once): a circular
+//            half range counts every unordered couple once.  The lane's six
+//            sums go to val[6][256]
+//   items    72 items per pair dealt to the 256 lanes: 66 step pairs (t, u),
+//            each a walk over the K slots (2 ds_read_b64 and two square roots
+//            per draw) and the squared difference from the target's variogram;
+//            6 column sums over the K lanes' val entries, in k order
+//   finish   one lane per pair adds the 66 terms in order, scales the six sums
+//            and writes the pair's 8 figures
+// The 32-pair cap is the LDS budget (the items' rows [32][73] and, for the
+// mixture head, 19 KB of factors next to the 24 KB of draws: 58 KB); it leaves
+// lanes idle only below K = 8.  Square roots: sqrtf against the target (as
+// g2k_bestk.hip), v_sqrt_f32 (1 ulp) among the draws and in the variogram.
+// Scene sums: per-workgroup rows [S * C][8] in the caller's workspace, then
+// g2k_scores_rows_kernel adds a scene's C rows in chunk order; C == 1 writes
+// out directly.
+#include "g2k_common.h"
+#include "g2k_head_draw.h"
+#include "g2k_scores.h"
+
+namespace g2k {
+namespace {
+
+constexpr int kScThreads = 256;
+constexpr int kScMaxG = 32;                   // pairs per pass: the LDS budget
+constexpr int kScPitch = kL2;                 // floats per draw in LDS (96 B: ds_read_b128 aligned)
+constexpr int kScStepPairs = kL * (kL - 1) / 2;   // 66
+constexpr int kScItems = kScStepPairs + 6;    // per pair: the step pairs, then the six column sums
+constexpr int kScVtPitch = kScItems + 1;      // odd: the finishing lanes' reads do not collide
+constexpr int kScPasses = 4;                  // passes that a workgroup's frames are sized for
+constexpr int kScLdsBytes = (kScThreads * kScPitch + 6 * kScThreads + kScMaxG * kScVtPitch + 4 * 8) * 4;
+
+struct ScoresGeom { int G, FC, C; };
+
+inline ScoresGeom scores_geom(const g2k_dims& d, int K) {
+  ScoresGeom g;
+  g.G = kScThreads / K;
+  if (g.G > kScMaxG) g.G = kScMaxG;
+  int fc = (kScPasses * g.G) / d.Nmax;
+  if (fc > d.F) fc = d.F;
+  if (fc < 1) fc = 1;
+  g.FC = fc;
+  g.C = d.F > 0 ? (d.F + fc - 1) / fc : 1;
+  return g;
+}
+
+__device__ __forceinline__ float sqrt_ulp(float x) { return __builtin_amdgcn_sqrtf(x); }
+
+template <class Head>
+__global__ void __launch_bounds__(kScThreads) sample_scores_kernel(
+    const float* __restrict__ pred, const float* __restrict__ targets,
+    const int32_t* __restrict__ n_active, const int32_t* __restrict__ n_frames,
+    const uint8_t* __restrict__ ped_mask, const float* __restrict__ head_params, int F, int Nmax,
+    int FC, int C, int G, int K, uint32_t seed_lo, uint32_t seed_hi, int shared_targets, float invK,
+    float invKK, float* __restrict__ per_ped, float* __restrict__ rows) {
+  __shared__ typename Head::Lds hlds;
+  __shared__ __attribute__((aligned(16))) float xy[kScThreads * kScPitch];
+  __shared__ float val[6][kScThreads];
+  __shared__ float vt[kScMaxG * kScVtPitch];
+  __shared__ float part[kScThreads / 64][8];
+  const int tid = threadIdx.x;
+  const int s = blockIdx.x / C, c = blockIdx.x - s * C;
+  const int f0 = c * FC;
+  const int fcn = min(FC, F - f0);                         // frames of this chunk (0 when F == 0)
+  const int nact = clampi(n_active[s], 0, Nmax);
+  const int nf = n_frames ? clampi(n_frames[s], 0, F) : F;
+  const int nfc = clampi(nf - f0, 0, fcn);                 // ... of them below n_frames
+  const uint8_t* mask = ped_mask ? ped_mask + (size_t)s * Nmax : nullptr;
+
+  Head::template stage<kScThreads>(head_params, hlds, tid);
+  // non-pairs: zeros in per_ped
+  if (per_ped) {
+    for (int idx = tid; idx < fcn * Nmax; idx += kScThreads) {
+      const int fl = idx / Nmax, n = idx - fl * Nmax;
+      const bool pair = fl < nfc && n < nact && (mask ? mask[n] != 0 : true);
+      if (pair) continue;
+      const size_t sf = (size_t)s * F + f0 + fl;
+      float4* o = reinterpret_cast<float4*>(per_ped) + (sf * Nmax + n) * 2;
+      o[0] = make_float4(0.f, 0.f, 0.f, 0.f);
+      o[1] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+  __syncthreads();
+  Head head;
+  head.bind(hlds);
+
+  const int g = tid / K, k = tid - g * K;                  // this lane's pair of the pass and its draw
+  const int npairs = nfc * nact;
+  const uint32_t lo = seed_lo + (uint32_t)k;               // (seed + k) mod 2^64
+  const uint32_t hi = seed_hi + (lo < seed_lo ? 1u : 0u);
+  // the partners of draw k: the next h draws, circularly
+  const int h = (K - 1) / 2 + ((K & 1) == 0 && k < K / 2 ? 1 : 0);
+  float acc[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) acc[i] = 0.f;
+#pragma nounroll
+  for (int base = 0; base < npairs; base += G) {           // uniform trip count
+    const int gp = min(G, npairs - base);                  // pairs of this pass
+    // ---- draw ----
+    const int p = base + g;
+    const bool valid = g < gp;
+    const int fl = valid ? p / nact : 0, n = valid ? p - fl * nact : 0;
+    const bool on = valid && (mask ? mask[n] != 0 : true);
+    float x[kL2];
+    float ta = 0.f, tf = 0.f, tr = 0.f;
+    if (on) {
+      const size_t sf = (size_t)s * F + f0 + fl;
+      const int64_t e0 = (int64_t)(sf * kL) * Nmax + n;    // element of step 0
+      float mu[kL2], tg[kL2];
+      load_mu_tg(true, pred, targets, sf, shared_targets ? (size_t)s : sf, n, Nmax, mu, tg);
+      head.draw(lo, hi, e0, Nmax, mu, [&](int t, float px, float py) {
+        x[2 * t] = px;
+        x[2 * t + 1] = py;
+        const float dx = px - tg[2 * t], dy = py - tg[2 * t + 1];
+        const float d2 = fmaf(dx, dx, dy * dy);
+        tf = sqrtf(d2);
+        ta += tf;
+        tr += d2;
+      });
+      tr = sqrtf(tr);
+      float4* o = reinterpret_cast<float4*>(xy + tid * kScPitch);
+#pragma unroll
+      for (int q = 0; q < kL2 / 4; ++q)
+        o[q] = make_float4(x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < kL2; ++i) x[i] = 0.f;
+    }
+    __syncthreads();
+    // ---- couples ----
+    float pa = 0.f, pf = 0.f, pr = 0.f;
+    if (on) {
+      int l = k;
+#pragma nounroll
+      for (int j = 0; j < h; ++j) {
+        l = l + 1 == K ? 0 : l + 1;
+        const float4* q4 = reinterpret_cast<const float4*>(xy + (g * K + l) * kScPitch);
+        float r2 = 0.f, sa = 0.f, last = 0.f;
+#pragma unroll
+        for (int q = 0; q < kL2 / 4; ++q) {
+          const float4 v = q4[q];
+          const float ax = x[4 * q] - v.x, ay = x[4 * q + 1] - v.y;
+          const float bx = x[4 * q + 2] - v.z, by = x[4 * q + 3] - v.w;
+          const float a2 = fmaf(ax, ax, ay * ay), b2 = fmaf(bx, bx, by * by);
+          last = sqrt_ulp(b2);
+          sa += sqrt_ulp(a2) + last;
+          r2 += a2 + b2;
+        }
+        pa += sa;
+        pf += last;
+        pr += sqrt_ulp(r2);
+      }
+    }
+    val[0][tid] = ta; val[1][tid] = tf; val[2][tid] = tr;
+    val[3][tid] = pa; val[4][tid] = pf; val[5][tid] = pr;
+    __syncthreads();
+    // ---- items ----
+    for (int idx = tid; idx < gp * kScItems; idx += kScThreads) {
+      const int gi = idx / kScItems, i = idx - gi * kScItems;
+      const int pp = base + gi;
+      const int fl2 = pp / nact, n2 = pp - fl2 * nact;
+      float v = 0.f;
+      if (mask ? mask[n2] != 0 : true) {
+        const int slot0 = gi * K;
+        float sum = 0.f;
+        if (i < kScStepPairs) {
+          int t = 0, r = i;                                // item i = the i-th (t, u), t < u
+          while (r >= kL - 1 - t) { r -= kL - 1 - t; ++t; }
+          const int u = t + 1 + r;
+          const float* row = xy + slot0 * kScPitch;
+#pragma nounroll
+          for (int kk = 0; kk < K; ++kk) {
+            const float2 a = *reinterpret_cast<const float2*>(row + kk * kScPitch + 2 * t);
+            const float2 b = *reinterpret_cast<const float2*>(row + kk * kScPitch + 2 * u);
+            const float dx = a.x - b.x, dy = a.y - b.y;
+            sum += sqrt_ulp(sqrt_ulp(fmaf(dx, dx, dy * dy)));
+          }
+          const size_t tf2 = shared_targets ? (size_t)s : (size_t)s * F + f0 + fl2;
+          const float2* t2 = reinterpret_cast<const float2*>(targets) + (tf2 * Nmax + n2) * kL;
+          const float2 ya = t2[t], yb = t2[u];
+          const float dx = ya.x - yb.x, dy = ya.y - yb.y;
+          const float e = sqrt_ulp(sqrt_ulp(fmaf(dx, dx, dy * dy))) - sum * invK;
+          v = e * e;
+        } else {
+          const float* col = val[i - kScStepPairs] + slot0;
+#pragma nounroll
+          for (int kk = 0; kk < K; ++kk) sum += col[kk];
+          v = sum;
+        }
+      }
+      vt[gi * kScVtPitch + i] = v;
+    }
+    __syncthreads();
+    // ---- finish: lane tid < gp takes pair base + tid (vt is next written after
+    // the following pass's two barriers)
+    if (tid < gp) {
+      const int pp = base + tid;
+      const int fl3 = pp / nact, n3 = pp - fl3 * nact;
+      if (mask ? mask[n3] != 0 : true) {
+        const float* w = vt + tid * kScVtPitch;
+        float vs = 0.f;
+#pragma unroll 6
+        for (int i = 0; i < kScStepPairs; ++i) vs += w[i];
+        const float sa = invK * (1.0f / 12.0f), pa12 = invKK * (1.0f / 12.0f);
+        const float4 m = make_float4(w[kScStepPairs] * sa, w[kScStepPairs + 1] * invK,
+                                     w[kScStepPairs + 2] * invK, w[kScStepPairs + 3] * pa12);
+        const float4 q = make_float4(w[kScStepPairs + 4] * invKK, w[kScStepPairs + 5] * invKK, vs, 0.f);
+        if (per_ped) {
+          const size_t sf = (size_t)s * F + f0 + fl3;
+          float4* o = reinterpret_cast<float4*>(per_ped) + (sf * Nmax + n3) * 2;
+          o[0] = m;
+          o[1] = q;
+        }
+        acc[0] += m.x; acc[1] += m.y; acc[2] += m.z; acc[3] += m.w;
+        acc[4] += q.x; acc[5] += q.y; acc[6] += q.z; acc[7] += 1.f;
+      }
+    }
+  }
+  // the workgroup's row: lanes by butterfly, waves in order
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const float v = wave_sum(acc[i]);
+    if ((tid & 63) == 0) part[tid >> 6][i] = v;
+  }
+  __syncthreads();
+  if (tid < 8)
+    rows[(size_t)blockIdx.x * 8 + tid] = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
+}
+
+// out[s][i] = sum over the scene's C chunk rows, in chunk order
+__global__ void __launch_bounds__(256) g2k_scores_rows_kernel(const float* __restrict__ rows, int S,
+                                                              int C, float* __restrict__ out) {
+  const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (id >= (int64_t)S * 8) return;
+  const int64_t s = id >> 3;
+  const int i = (int)(id & 7);
+  float v = 0.f;
+  for (int c = 0; c < C; ++c) v += rows[((size_t)s * C + c) * 8 + i];
+  out[id] = v;
+}
+
+template <class Head>
+int sample_scores_launch(const g2k_dims* d, const float* pred, const float* targets,
+                         const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                         const float* head_params, uint64_t seed, int K, float* per_ped, float* out,
+                         float* rows, hipStream_t st) {
+  const ScoresGeom g = scores_geom(*d, K);
+  const int64_t wgs = (int64_t)d->S * g.C;
+  if (wgs > 0x7fffffff)
+    return set_err(G2K_EINVAL, "%ssample_scores: %lld workgroups", Head::kPrefix, (long long)wgs);
+  const float invK = (float)(1.0 / (double)K);
+  const float invKK = (float)(2.0 / ((double)K * (double)(K - 1)));
+  hipLaunchKernelGGL(sample_scores_kernel<Head>, dim3((unsigned)wgs), dim3(kScThreads), 0, st, pred,
+                     targets, n_active, n_frames, ped_mask, head_params, d->F, d->Nmax, g.FC, g.C, g.G,
+                     K, (uint32_t)seed, (uint32_t)(seed >> 32),
+                     (d->flags & G2K_STEP_TARGETS_SHARED) ? 1 : 0, invK, invKK, per_ped,
+                     g.C == 1 ? out : rows);
+  int rc = check_launch("sample_scores_kernel");
+  if (rc || g.C == 1) return rc;
+  hipLaunchKernelGGL(g2k_scores_rows_kernel, dim3((unsigned)(((int64_t)d->S * 8 + 255) / 256)),
+                     dim3(256), 0, st, rows, d->S, g.C, out);
+  return check_launch("g2k_scores_rows_kernel");
+}
+
+bool scores_dims_ok(const g2k_dims* d) {
+  return d->S >= 0 && d->F >= 0 && d->Nmax >= 1 && d->Nmax <= kMaxN;
+}
+
+// one row [8] per (scene, chunk); FC >= 1 frame per chunk, so at most F chunks
+int64_t scores_ws_bytes(const g2k_dims* d) {
+  return (int64_t)d->S * (d->F > 1 ? d->F : 1) * 8 * 4;
+}
+
+// the argument checks, before any HIP call; G2K_OK with S > 0: launch
+int scores_validate(const char* name, const g2k_dims* d, const void* pred, const void* targets,
+                    const void* n_active, const void* head, int32_t K, const void* per_ped,
+                    const void* out, const void* workspace, int64_t workspace_bytes) {
+  if (!d) return set_err(G2K_EINVAL, "dims is NULL");
+  if (d->flags & ~G2K_STEP_TARGETS_SHARED)
+    return set_err(G2K_EUNSUPPORTED, "%s: flags %d (0 or G2K_STEP_TARGETS_SHARED)", name, d->flags);
+  if (!scores_dims_ok(d)) return set_err(G2K_EINVAL, "S=%d F=%d Nmax=%d", d->S, d->F, d->Nmax);
+  if (K < G2K_SCORES_KMIN || K > G2K_SCORES_KMAX)
+    return set_err(G2K_EINVAL, "K=%d (%d..%d)", K, G2K_SCORES_KMIN, G2K_SCORES_KMAX);
+  if (!pred || !targets || !n_active || !head || !out)
+    return set_err(G2K_EINVAL, "a required buffer pointer is NULL");
+  if (((uintptr_t)targets) & 7) return set_err(G2K_EINVAL, "targets must be 8-byte aligned");
+  if (((uintptr_t)per_ped) & 15) return set_err(G2K_EINVAL, "per_ped must be 16-byte aligned");
+  if (workspace && (((uintptr_t)workspace) & 3))
+    return set_err(G2K_EINVAL, "workspace must be 4-byte aligned");
+  const int64_t need = scores_ws_bytes(d);
+  if (d->S > 0 && (!workspace || workspace_bytes < need))
+    return set_err(G2K_EINVAL, "workspace of %lld bytes needed (got %lld)", (long long)need,
+                   (long long)workspace_bytes);
+  return G2K_OK;
+}
+
+template <class Head>
+int sample_scores(const char* name, const g2k_dims* d, const float* pred, const float* targets,
+                  const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                  const float* head, uint64_t seed, int32_t K, float* per_ped, float* out,
+                  void* workspace, int64_t workspace_bytes, void* stream) {
+  const int rc = scores_validate(name, d, pred, targets, n_active, head, K, per_ped, out, workspace,
+                                 workspace_bytes);
+  if (rc || d->S == 0) return rc;
+  return sample_scores_launch<Head>(d, pred, targets, n_active, n_frames, ped_mask, head, seed, K,
+                                    per_ped, out, static_cast<float*>(workspace), (hipStream_t)stream);
+}
+
+}  // namespace
+}  // namespace g2k
+
+using namespace g2k;
+
+extern "C" {
+
+int64_t g2k_sample_scores_workspace_bytes(const g2k_dims* d) {
+  if (!d || !scores_dims_ok(d)) return -1;
+  return scores_ws_bytes(d);
+}
+
+// the launch geometry (scores_geom: host arithmetic, no HIP call), as the
+// launcher works it out
+int g2k_sample_scores_geometry(const g2k_dims* d, int32_t K, int32_t* out) {
+  if (!d) return set_err(G2K_EINVAL, "dims is NULL");
+  if (!scores_dims_ok(d)) return set_err(G2K_EINVAL, "S=%d F=%d Nmax=%d", d->S, d->F, d->Nmax);
+  if (K < G2K_SCORES_KMIN || K > G2K_SCORES_KMAX)
+    return set_err(G2K_EINVAL, "K=%d (%d..%d)", K, G2K_SCORES_KMIN, G2K_SCORES_KMAX);
+  if (!out) return set_err(G2K_EINVAL, "out is NULL");
+  const ScoresGeom g = scores_geom(*d, K);
+  out[G2K_SCORES_GEOM_G] = g.G;
+  out[G2K_SCORES_GEOM_LANES] = K;
+  out[G2K_SCORES_GEOM_FC] = g.FC;
+  out[G2K_SCORES_GEOM_C] = g.C;
+  out[G2K_SCORES_GEOM_LDS_BYTES] = kScLdsBytes;
+  return G2K_OK;
+}
+
+int g2k_sample_scores_f32(const g2k_dims* d, const float* pred, const float* targets,
+                          const int32_t* n_active, const int32_t* n_frames,
+                          const uint8_t* ped_mask, const float* head, uint64_t seed, int32_t K,
+                          float* per_ped, float* out, void* workspace, int64_t workspace_bytes,
+                          void* stream) {
+  return sample_scores<PerStepHead>("sample_scores", d, pred, targets, n_active, n_frames, ped_mask,
+                                    head, seed, K, per_ped, out, workspace, workspace_bytes, stream);
+}
+
+int g2k_fullcov_sample_scores_f32(const g2k_dims* d, const float* pred, const float* targets,
+                                  const int32_t* n_active, const int32_t* n_frames,
+                                  const uint8_t* ped_mask, const float* chol, uint64_t seed,
+                                  int32_t K, float* per_ped, float* out, void* workspace,
+                                  int64_t workspace_bytes, void* stream) {
+  return sample_scores<FullCovHead>("fullcov_sample_scores", d, pred, targets, n_active, n_frames,
+                                    ped_mask, chol, seed, K, per_ped, out, workspace, workspace_bytes,
+                                    stream);
+}
+
+int g2k_mix_sample_scores_f32(const g2k_dims* d, const float* pred, const float* targets,
+                              const int32_t* n_active, const int32_t* n_frames,
+                              const uint8_t* ped_mask, const float* mix, uint64_t seed, int32_t K,
+                              float* per_ped, float* out, void* workspace, int64_t workspace_bytes,
+                              void* stream) {
+  return sample_scores<MixHead>("mix_sample_scores", d, pred, targets, n_active, n_frames, ped_mask,
+                                mix, seed, K, per_ped, out, workspace, workspace_bytes, stream);
+}
+
+}  // extern "C"

@@ -52,7 +52,13 @@ negative log density under it, floored at --kde_floor (KDE_FIGURES: the mean
 over the 12 steps, the last step's, and the share of steps on the floor) — the
 one likelihood figure with the same definition for both heads, so with
 --fullcov_head a g2k_fullcov_kde_nll_f32 launch adds FULLCOV_KDE_FIGURES; unlike
-minADE_K it grows when the head is too wide.  The units caveat above holds for a pooled fit too: eth_hotel
+minADE_K it grows when the head is too wide.  --sample_scores 1 (2 <= K <= 256)
+adds the trajectory-level scores of the same K draws, one g2k_sample_scores_f32
+launch per head (csrc/g2k_scores.hip; SCORE_FIGURES): the fair energy score with
+the 24-D norm (strictly proper for the joint law of the 12 steps), with the ADE
+and the FDE (marginals only), the expected ADE / FDE of a draw, the average
+pairwise displacement and the variogram score of order 1/2, which is the one
+that sees whether a draw zig-zags.  The units caveat above holds for a pooled fit too: eth_hotel
 is normalised, the UCY sets are world coordinates, so a fold that mixes them
 fits one width to both.  The build's: the reference has no probabilistic head
 (SURVEY.md §8(f) row 4), so these figures have no reference counterpart.
@@ -82,6 +88,9 @@ MIX_FIGURES = ("mix_min_ade", "mix_min_fde", "mix_nll", "mix_components", "mix_w
                "mix_loglik_gain")
 MIX_JOINT_FIGURES = ("mix_jade", "mix_jfde", "mix_collision_rate", "mix_collision_rate_best")
 MIX_KDE_FIGURES = tuple("mix_" + k for k in KDE_FIGURES)
+SCORE_FIGURES = ("es_traj", "es_ade", "es_fde", "mean_ade", "mean_fde", "apd", "vs")
+FULLCOV_SCORE_FIGURES = tuple("fullcov_" + k for k in SCORE_FIGURES)
+MIX_SCORE_FIGURES = tuple("mix_" + k for k in SCORE_FIGURES)
 
 
 def calib_figures(hs):
@@ -120,6 +129,21 @@ def kde_figures(kd, prefix=""):
     MIX_KDE_FIGURES) of a KdeNll."""
     return {prefix + "kde_nll": kd.kde_nll, prefix + "kde_nll_final": kd.kde_nll_final,
             prefix + "kde_clipped": kd.clipped_share}
+
+
+def score_figures(sc, prefix=""):
+    """SCORE_FIGURES (``prefix`` "fullcov_": FULLCOV_SCORE_FIGURES, "mix_":
+    MIX_SCORE_FIGURES) of a scores.SampleScores."""
+    return {prefix + k: getattr(sc, k) for k in SCORE_FIGURES}
+
+
+def _score_line(name, K, dataset, res, prefix=""):
+    """The log line of one head's SCORE_FIGURES."""
+    v = {k: res[prefix + k] for k in SCORE_FIGURES}
+    return (f"{name} of the {K} draws on dataset {dataset}: energy score 24-D "
+            f"{v['es_traj']:.6g} ADE {v['es_ade']:.6g} FDE {v['es_fde']:.6g}, expected ADE / FDE of a "
+            f"draw {v['mean_ade']:.6g} / {v['mean_fde']:.6g}, APD {v['apd']:.6g}, variogram score "
+            f"{v['vs']:.6g}")
 
 
 def mixture_figures(mx, bk, st, fit):
@@ -196,6 +220,12 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
     --kde_nll 1 MIX_KDE_FIGURES from one MixtureHead.kde_nll launch, a log
     line each, after the mixture's line and with the other heads' K, seed,
     radius and floor (``keep["mixture"]["joint"]``, ``keep["mixture"]["kde"]``).
+    --sample_scores 1 (2 <= K <= 256) adds SCORE_FIGURES from one
+    GaussianHead.sample_scores launch (csrc/g2k_scores.hip; same predictions, K
+    and seed) after the per-step head's other figures, and FULLCOV_SCORE_FIGURES
+    / MIX_SCORE_FIGURES at the end of those heads' blocks, a log line each
+    (``keep["scores"]``, ``keep["fullcov"]["scores"]``,
+    ``keep["mixture"]["scores"]``).
     ``keep`` (a dict)
     receives the plan, the predictions, the head and the kernels' outputs for
     a caller that checks them."""
@@ -204,6 +234,9 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
         raise ValueError("--num_samples K must be >= 1")
     if getattr(args, "kde_nll", 0) and K < 4:
         raise ValueError("--kde_nll 1 needs --num_samples K >= 4")
+    want_scores = bool(getattr(args, "sample_scores", 0))
+    if want_scores and not 2 <= K <= 256:
+        raise ValueError("--sample_scores 1 needs --num_samples K with 2 <= K <= 256")
     fit_mode = getattr(args, "fit_head", "off") or "off"
     calibrate = bool(getattr(args, "calibration", 0)) or fit_mode != "off"
     plan = left_out_plan(args, params.nmax)
@@ -267,8 +300,14 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
             f"50% {res['coverage_50']:.4f} 90% {res['coverage_90']:.4f} 95% {res['coverage_95']:.4f}, "
             f"ECE {res['ece']:.4f}, q_ratio {res['q_ratio']:.6g}, sigma_x / sigma_y step 1 "
             f"{sig[0, 0]:.6g} / {sig[1, 0]:.6g} step 12 {sig[0, -1]:.6g} / {sig[1, -1]:.6g}")
+    scores = None
+    if want_scores:
+        scores = gh.sample_scores(out.pred, t["targets"], t["n_active"], K, seed=args.sample_seed,
+                                  n_frames=one, ped_mask=t["ped_mask"], want_per_ped=keep is not None)
+        res.update(score_figures(scores))
+        log(_score_line("sample scores", K, args.leaveDataset, res))
     fc_mode = getattr(args, "fullcov_head", "off") or "off"
-    fc = fc_st = fc_bk = fc_joint = fc_kde = None
+    fc = fc_st = fc_bk = fc_joint = fc_kde = fc_scores = None
     if fc_mode != "off":
         from .fullcov import FullCovHead
         fc = FullCovHead(device=device)
@@ -314,8 +353,14 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                 f"{res['kde_nll']:.6g}), final step {res['fullcov_kde_nll_final']:.6g} (per-step "
                 f"head {res['kde_nll_final']:.6g}), floor {kde_floor:g} reached by "
                 f"{res['fullcov_kde_clipped']:.4f} of the steps")
+        if want_scores:
+            fc_scores = fc.sample_scores(out.pred, t["targets"], t["n_active"], K,
+                                         seed=args.sample_seed, n_frames=one, ped_mask=t["ped_mask"],
+                                         want_per_ped=keep is not None)
+            res.update(score_figures(fc_scores, "fullcov_"))
+            log(_score_line("full-covariance sample scores", K, args.leaveDataset, res, "fullcov_"))
     mx_mode = getattr(args, "mixture_head", "off") or "off"
-    mx = mx_fit = mx_st = mx_bk = mx_joint = mx_kde = None
+    mx = mx_fit = mx_st = mx_bk = mx_joint = mx_kde = mx_scores = None
     if mx_mode != "off":
         from .mixture import MixtureHead
         mx = MixtureHead(components=int(getattr(args, "mixture_components", 3)), device=device)
@@ -362,6 +407,12 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                 f"{res['kde_nll']:.6g}), final step {res['mix_kde_nll_final']:.6g} (per-step "
                 f"head {res['kde_nll_final']:.6g}), floor {kde_floor:g} reached by "
                 f"{res['mix_kde_clipped']:.4f} of the steps")
+        if want_scores:
+            mx_scores = mx.sample_scores(out.pred, t["targets"], t["n_active"], K,
+                                         seed=args.sample_seed, n_frames=one, ped_mask=t["ped_mask"],
+                                         want_per_ped=keep is not None)
+            res.update(score_figures(mx_scores, "mix_"))
+            log(_score_line("mixture sample scores", K, args.leaveDataset, res, "mix_"))
     if keep is not None:
         keep.update(plan=plan, pred=out.pred, head=gh.head, out=bk, n_frames=np.ones(S, np.int32),
                     joint=joint)
@@ -371,16 +422,22 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                 keep["mixture"]["joint"] = mx_joint
             if mx_kde is not None:
                 keep["mixture"]["kde"] = mx_kde
+            if mx_scores is not None:
+                keep["mixture"]["scores"] = mx_scores
         if calibrate:
             keep.update(calib=calib, fitted=fitted)
         if kde is not None:
             keep.update(kde=kde)
+        if scores is not None:
+            keep.update(scores=scores)
         if fc is not None:
             keep.update(fullcov=dict(stats=fc_st, out=fc_bk, fitted=ffit), fullcov_chol=fc.chol)
             if fc_joint is not None:
                 keep["fullcov"]["joint"] = fc_joint
             if fc_kde is not None:
                 keep["fullcov"]["kde"] = fc_kde
+            if fc_scores is not None:
+                keep["fullcov"]["scores"] = fc_scores
     return res
 
 

@@ -298,6 +298,19 @@ class FullCovHead:
         return _kde_nll("g2k_fullcov_kde_nll_f32", self.chol, d, pred, targets, n_active, k, seed,
                         log_floor, n_frames, ped_mask, want_per_ped, stream)
 
+    def sample_scores(self, pred, targets, n_active, k, seed=0, *, n_frames=None, ped_mask=None,
+                      want_per_ped=False, targets_shared=False, stream=None):
+        """Energy, variogram and diversity scores in one launch
+        (g2k_fullcov_sample_scores_f32): GaussianHead.sample_scores over this
+        head's correlated draws ``sample(pred, seed + i)``, i < k ->
+        scores.SampleScores."""
+        from .scores import _sample_scores
+        d = self._dims(pred)
+        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
+        self._check_chol(pred.device)
+        return _sample_scores("g2k_fullcov_sample_scores_f32", self.chol, d, pred, targets, n_active,
+                              k, seed, n_frames, ped_mask, want_per_ped, stream)
+
     def joint_eval(self, pred, targets, n_active, k, radius, seed=0, *, n_frames=None, ped_mask=None,
                    targets_shared=False, want_per_frame=True, stream=None):
         """Joint best-of-K evaluation in one launch (g2k_fullcov_joint_eval_f32):

@@ -433,6 +433,18 @@ class GaussianHead:
         return _kde_nll("g2k_kde_nll_f32", self.head, d, pred, targets, n_active, k, seed, log_floor,
                         n_frames, ped_mask, want_per_ped, stream)
 
+    def sample_scores(self, pred, targets, n_active, k, seed=0, *, n_frames=None, ped_mask=None,
+                      want_per_ped=False, targets_shared=False, stream=None):
+        """Energy, variogram and diversity scores of the K draws
+        ``sample(pred, seed + i)``, i < k, in one launch (g2k_sample_scores_f32,
+        csrc/g2k_scores.hip) -> scores.SampleScores.  k in 2..256."""
+        from .scores import _sample_scores
+        d = self._dims(pred)
+        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
+        _check_dev("head", self.head, pred.device, torch.float32)
+        return _sample_scores("g2k_sample_scores_f32", self.head, d, pred, targets, n_active, k, seed,
+                              n_frames, ped_mask, want_per_ped, stream)
+
     def joint_eval(self, pred, targets, n_active, k, radius, seed=0, *, n_frames=None, ped_mask=None,
                    targets_shared=False, want_per_frame=True, stream=None):
         """Joint best-of-K evaluation in one launch (g2k_joint_eval_f32): draw

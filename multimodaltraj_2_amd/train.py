@@ -48,7 +48,8 @@
   minADE_K / minFDE_K, one g2k_best_of_k_f32 launch; with --collision_radius
   R > 0 also JADE_K / JFDE_K and the collision rates, one g2k_joint_eval_f32
   launch; with --kde_nll 1 also the KDE-NLL of the K draws, one g2k_kde_nll_f32
-  launch).
+  launch; with --sample_scores 1 also their energy, variogram and diversity
+  scores, one g2k_sample_scores_f32 launch).
 
 The model weights are one seeded N(0, 1) draw (quirk Q15: the reference
 re-draws them every batch), padded to Nmax (8 for the node slice).
