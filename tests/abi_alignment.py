@@ -1,4 +1,5 @@
-"""The pointer alignment every entry point of include/g2k_hip.h accepts, as
+"""The pointer alignment every entry point of include/g2k_hip.h,
+include/g2k_mix.h and include/g2k_scores.h accepts, as
 data (tests/test_abi_alignment.py drives the validators with it on the CPU,
 tests/test_abi_alignment_gpu.py runs every entry point at exactly these
 minima against its 16-byte-aligned twin and the float64 oracle).
@@ -26,8 +27,8 @@ is searched for, not a line number, so the row survives edits above it and
 fails (test_every_quoted_check_is_in_the_source) when the check itself goes.
 ``cond`` = (label, dims that select the case, minimum, state, where): the
 requirement under a condition on the dims, e.g. 16 when D == 16, else 4.
-A claim is what include/g2k_hip.h promises; it is never edited to follow the
-library.
+A claim is what the header that declares the entry point promises; it is never
+edited to follow the library.
 
 ``accept``: how a call whose every pointer sits at its minimum shows that it
 was accepted without any HIP call being reached with the made-up pointers:
@@ -40,7 +41,7 @@ from __future__ import annotations
 
 from dataclasses import dataclass, field
 
-ABI, DATA, SCENE = "g2k_abi.hip", "g2k_data.hip", "g2k_scene.hip"
+ABI, DATA, SCENE, SCORES = "g2k_abi.hip", "g2k_data.hip", "g2k_scene.hip", "g2k_scores.hip"
 ELEM_BYTES = {"f32": 4, "i32": 4, "u8": 1, "f64": 8, "i64": 8, "void": 1}
 
 # the three alignment-dependent branches of the scene kernel
@@ -62,6 +63,18 @@ SWS4 = (ABI, "if (workspace && (((uintptr_t)workspace) & 3))")
 DBL8 = (ABI, "if ((((uintptr_t)moments) | ((uintptr_t)stats) | ((uintptr_t)inside) | ((uintptr_t)r2)) & 7)")
 STWS8 = (ABI, "if (workspace && (((uintptr_t)workspace) & 7))")
 GATHER8 = (DATA, "if (((uintptr_t)xy & 7u) || ((uintptr_t)pos & 7u) || ((uintptr_t)targets & 7u))")
+# g2k_mix_em_f32's own (each quote runs into a neighbouring line that only that
+# entry point has, so the validators with the same check do not stand in for it)
+EM_TGT8 = (ABI, 'if (!r.p) return set_err(G2K_EINVAL, "%s is NULL", r.name);\n'
+                '  if (((uintptr_t)targets) & 7) return set_err(G2K_EINVAL, "targets must be 8-byte aligned");')
+EM_DBL8 = (ABI, "if ((((uintptr_t)moments) | ((uintptr_t)resp) | ((uintptr_t)total)) & 7)")
+EM_WS8 = (ABI, 'if (workspace && (((uintptr_t)workspace) & 7))\n'
+               '    return set_err(G2K_EINVAL, "workspace must be 8-byte aligned");\n'
+               "  const int64_t need = mix_em_ws_bytes(d);")
+# scores_validate
+SC_TGT8 = (SCORES, 'if (((uintptr_t)targets) & 7) return set_err(G2K_EINVAL, "targets must be 8-byte aligned");')
+SC_PERPED16 = (SCORES, 'if (((uintptr_t)per_ped) & 15) return set_err(G2K_EINVAL, "per_ped must be 16-byte aligned");')
+SC_WS4 = (SCORES, "if (workspace && (((uintptr_t)workspace) & 3))")
 
 
 @dataclass(frozen=True)
@@ -208,8 +221,8 @@ ENTRIES = (
 )
 
 
-def _pairs(head):
-    return ("dims", c4("pred"), Arg("targets", "f32", 8, "a", TGT8, note="float2 reads"),
+def _pairs(head, tgt8=TGT8):
+    return ("dims", c4("pred"), Arg("targets", "f32", 8, "a", tgt8, note="float2 reads"),
             c4("n_active", "i32"), c4("n_frames", "i32"), Arg("ped_mask", "u8", 1, "c"), c4(head))
 
 
@@ -264,9 +277,42 @@ ENTRIES += (
            Arg("ped_mask", "u8", 1, "c"), STREAM)),
 )
 
+# --- include/g2k_mix.h: the Gaussian-mixture head ---------------------------
+def _dbl8(name):
+    return Arg(name, "f64", 8, "a", EM_DBL8)
+
+
+def _scores(name, head):
+    return Entry(name, _pairs(head, SC_TGT8) + (
+        Val("seed", 7), Val("K", 5), Arg("per_ped", "f32", 16, "a", SC_PERPED16, note="two float4 stores a pair"),
+        c4("out"), Arg("workspace", "void", 4, "a", SC_WS4, note="float rows"),
+        Val("workspace_bytes", 1 << 30), STREAM), dims=BASE)
+
+
+ENTRIES += (
+    Entry("g2k_mix_em_f32",
+          _pairs("mix_in", EM_TGT8)[:-1] + (
+              # "mix_in and mix_out must be 4-byte aligned" restates the natural
+              # alignment (tests/test_mixture.py holds that check): state "c"
+              c4("mix_in", note="w, b and the factors: 4-byte loads"), _dbl8("moments"), _dbl8("resp"),
+              _dbl8("total"), c4("mix_out", note="4-byte stores; may be NULL"),
+              Arg("workspace", "void", 8, "a", EM_WS8, note="the responsibilities and the workgroups' rows: doubles"),
+              Val("workspace_bytes", 1 << 30), STREAM),
+          dims=BASE),
+    Entry("g2k_mix_sample_f32",
+          ("dims", c4("pred"), c4("mix"), Val("seed", 3), c4("out"), c4("comp", "i32"), STREAM), dims=BASE),
+    _marginal("g2k_mix_best_of_k_f32", "mix"),
+    _joint("g2k_mix_joint_eval_f32", "mix"),
+    _kde("g2k_mix_kde_nll_f32", "mix"),
+    # --- include/g2k_scores.h: the sample scores of the three heads ---
+    _scores("g2k_sample_scores_f32", "head"),
+    _scores("g2k_fullcov_sample_scores_f32", "chol"),
+    _scores("g2k_mix_sample_scores_f32", "mix"),
+)
+
 BY_NAME = {e.name: e for e in ENTRIES}
 
-# entry points of the header without a device pointer (planning calls, host
+# entry points of the headers without a device pointer (planning calls, host
 # arithmetic) or with host pointers only (g2k_walk.cpp: out of scope here)
 NO_DEVICE_POINTERS = (
     "g2k_abi_version", "g2k_last_error", "g2k_step_lds_bytes", "g2k_step_workspace_bytes",
@@ -277,4 +323,7 @@ NO_DEVICE_POINTERS = (
     "g2k_kde_nll_workspace_bytes", "g2k_fullcov_kde_nll_workspace_bytes",
     "g2k_head_stats_workspace_bytes", "g2k_fullcov_stats_workspace_bytes", "g2k_best_of_k_geometry",
     "g2k_context_conv_workspace_bytes", "g2k_traj_create", "g2k_traj_destroy", "g2k_traj_next_step",
-    "g2k_traj_sample_scenes")
+    "g2k_traj_sample_scenes",
+    # include/g2k_mix.h, include/g2k_scores.h
+    "g2k_mix_em_workspace_bytes", "g2k_mix_best_of_k_workspace_bytes", "g2k_mix_joint_eval_workspace_bytes",
+    "g2k_mix_kde_nll_workspace_bytes", "g2k_sample_scores_workspace_bytes", "g2k_sample_scores_geometry")

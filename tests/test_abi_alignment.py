@@ -8,10 +8,16 @@ its argument checks, or is an empty batch).
   success the size check that follows the alignment checks;
 * rejected below it: the same call with ONE state-"a" pointer at half its
   minimum is G2K_EINVAL and the message names the argument;
-* the table covers the header: every declared entry point and every pointer
-  parameter of it, with the check or branch each row quotes present in the
-  source it names, and include/g2k_hip.h stating every validated requirement
-  in the entry point's "Alignment (bytes) of ..." sentence.
+* the table covers the headers (include/g2k_hip.h, and the two that declare
+  what is bound by symbol: include/g2k_mix.h, include/g2k_scores.h): every
+  declared entry point and every pointer parameter of it, with the check or
+  branch each row quotes present in the source it names, and the header that
+  declares an entry point stating every validated requirement in that entry
+  point's "Alignment (bytes) of ..." sentence.
+
+Every symbol is reached through the binding that sets its argument types:
+_lib.load() for g2k_hip.h, mixture.load() for g2k_mix.h, scores.load() for
+g2k_scores.h.
 """
 import ctypes
 import os
@@ -19,12 +25,39 @@ import re
 
 import pytest
 
-from multimodaltraj_2_amd import _lib
+from multimodaltraj_2_amd import _lib, mixture, scores
 from tests import abi_alignment as al
 from tests.test_abi import HEADER, ROOT, declared_functions
 
 CSRC = os.path.join(ROOT, "multimodaltraj_2_amd", "csrc")
 EINVAL = -1
+# header -> the binding of its symbols
+BINDINGS = {HEADER: _lib.load,
+            os.path.join(ROOT, "include", "g2k_mix.h"): mixture.load,
+            os.path.join(ROOT, "include", "g2k_scores.h"): scores.load}
+HEADERS = tuple(BINDINGS)
+
+
+def uncommented(header):
+    return re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
+
+
+def declared_in():
+    """{function: the header that declares it}; no function is declared twice."""
+    out = {}
+    for h in HEADERS:
+        for fn in set(re.findall(r"\b(g2k_[a-z0-9_]+)\s*\(", uncommented(h))):
+            assert fn not in out, (fn, h, out[fn])
+            out[fn] = h
+    return out
+
+
+DECLARED_IN = declared_in()
+
+
+def bound(entry):
+    """The library handle, through the binding of the header that declares `entry`."""
+    return BINDINGS[DECLARED_IN[entry.name]]()
 
 
 def resolve(entry, cond):
@@ -41,15 +74,17 @@ def resolve(entry, cond):
 
 
 def call(lib, entry, cond, moved=None):
-    """Call `entry` with every pointer at 4096 k + its minimum (a different k
-    per argument), `moved` = (name, offset) at 4096 k + offset instead."""
+    """Call `entry` with every pointer at 65536 k + its minimum (a different k
+    per argument; no two ranges an entry point checks for overlap meet: the
+    mixture block is 19456 bytes), `moved` = (name, offset) at 65536 k + offset
+    instead."""
     dims, req = resolve(entry, cond)
     keep, k = [], [0]
 
     def value(a):
         k[0] += 1
         off = moved[1] if moved and moved[0] == a.name else req[a.name][0]
-        return 4096 * k[0] + off
+        return 65536 * k[0] + off
 
     argv = []
     for p in entry.params:
@@ -73,7 +108,7 @@ CASE_IDS = [e.name + ("" if c is None else "-" + c) for e, c in CASES]
 
 @pytest.mark.parametrize("entry,cond", CASES, ids=CASE_IDS)
 def test_accepted_at_the_minimum(entry, cond):
-    lib = _lib.load()
+    lib = bound(entry)
     rc, msg = call(lib, entry, cond)
     if entry.accept == "ok":
         assert rc == 0, (rc, msg)
@@ -87,7 +122,7 @@ REJECTIONS = [(e, c, a.name) for e, c in CASES for a in e.args if resolve(e, c)[
 @pytest.mark.parametrize("entry,cond,name", REJECTIONS,
                          ids=[e.name + ("" if c is None else "-" + c) + "-" + n for e, c, n in REJECTIONS])
 def test_rejected_below_the_minimum(entry, cond, name):
-    lib = _lib.load()
+    lib = bound(entry)
     need = resolve(entry, cond)[1][name][0]
     arg = next(a for a in entry.args if a.name == name)
     rc, msg = call(lib, entry, cond, moved=(name, need // 2))
@@ -126,23 +161,28 @@ def test_every_quoted_check_is_in_the_source():
 
 
 def prototypes():
-    """{function: [(type, name), ...]} of the header's declarations."""
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    """{function: [(type, name), ...]} of the three headers' declarations."""
     out = {}
-    for m in re.finditer(r"\b(g2k_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text):
-        params = []
-        for p in m.group(2).split(","):
-            p = " ".join(p.split())
-            if p and p != "void":
-                t, n = p.rsplit(" ", 1)
-                params.append((t, n))
-        out[m.group(1)] = params
+    for h in HEADERS:
+        for m in re.finditer(r"\b(g2k_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", uncommented(h)):
+            params = []
+            for p in m.group(2).split(","):
+                p = " ".join(p.split())
+                if p and p != "void":
+                    t, n = p.rsplit(" ", 1)
+                    params.append((t, n))
+            assert m.group(1) not in out and DECLARED_IN[m.group(1)] == h, m.group(1)
+            out[m.group(1)] = params
     return out
 
 
 def test_table_covers_every_pointer_of_every_entry_point():
     protos = prototypes()
-    assert sorted(list(al.BY_NAME) + list(al.NO_DEVICE_POINTERS)) == declared_functions()
+    assert sorted(list(al.BY_NAME) + list(al.NO_DEVICE_POINTERS)) == sorted(DECLARED_IN)
+    assert sorted(protos) == sorted(DECLARED_IN)           # every declaration parsed as a prototype
+    assert sorted(fn for fn, h in DECLARED_IN.items() if h == HEADER) == declared_functions()
+    for h, n in ((HEADERS[1], 9), (HEADERS[2], 5)):        # what g2k_mix.h and g2k_scores.h declare
+        assert sum(v == h for v in DECLARED_IN.values()) == n, h
     for e in al.ENTRIES:
         want = [n for t, n in protos[e.name] if "*" in t and n not in ("d", "w", "stream")]
         got = [p.name for p in e.params if isinstance(p, al.Arg)]
@@ -157,15 +197,18 @@ def test_table_covers_every_pointer_of_every_entry_point():
 
 
 def alignment_sentences():
-    """{entry point: text} of the header's "Alignment (bytes) of A[, B and C]:
-    ... ." sentences (inside comments)."""
+    """{entry point: text} of the headers' "Alignment (bytes) of A[, B and C]:
+    ... ." sentences (inside comments); an entry point's sentence stands in the
+    header that declares it."""
     out = {}
-    for block in re.findall(r"/\*.*?\*/", open(HEADER).read(), flags=re.S):
-        flat = " ".join(line.strip().lstrip("*").strip() for line in block.splitlines())
-        for m in re.finditer(r"Alignment \(bytes\) of ([^:]*):(.*?)\.(?= |$)", flat):
-            for fn in re.findall(r"g2k_[a-z0-9_]+", m.group(1)):
-                assert fn not in out, fn
-                out[fn] = m.group(2)
+    for h in HEADERS:
+        for block in re.findall(r"/\*.*?\*/", open(h).read(), flags=re.S):
+            flat = " ".join(line.strip().lstrip("*").strip() for line in block.splitlines())
+            for m in re.finditer(r"Alignment \(bytes\) of ([^:]*):(.*?)\.(?= |$)", flat):
+                for fn in re.findall(r"g2k_[a-z0-9_]+", m.group(1)):
+                    assert fn not in out, fn
+                    assert DECLARED_IN.get(fn) == h, (fn, "sentence in", h, "declared in", DECLARED_IN.get(fn))
+                    out[fn] = m.group(2)
     return out
 
 

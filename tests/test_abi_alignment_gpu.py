@@ -1,5 +1,6 @@
-"""GPU: every entry point at the weakest pointer alignment its validator
-accepts (tests/abi_alignment.py), through the raw C ABI.
+"""GPU: every entry point of include/g2k_hip.h, include/g2k_mix.h and
+include/g2k_scores.h at the weakest pointer alignment its validator accepts
+(tests/abi_alignment.py), through the raw C ABI.
 
 Each case launches twice from the same host arrays, every buffer — inputs,
 outputs, in/out state and workspaces — an ``Arena`` payload between poisoned
@@ -7,7 +8,8 @@ guards: once with every buffer on a 16-byte boundary (+0), once with the
 case's buffers moved to their minimum (float32 / int32 +4, +8 where the
 minimum is 8; float64 / int64 +8; ped_mask +1, +2, +3; an argument whose
 minimum is 16 stays at +0 — ``offsets_at_minimum`` reads them from the
-table, so no case can pass a pointer its validator rejects).  It asserts
+table, so no case can pass a pointer its validator rejects; the EM step and
+the sample scores run with ped_mask at all three, ``every_mask``).  It asserts
 
 * the minimum-alignment outputs are BIT-IDENTICAL to the +0 outputs (the
   poison of the elements that are not written included): alignment changes how
@@ -59,6 +61,15 @@ bound) and the quantity that gives it:
   tests/kde_ref.py's gate; each of the 2 x 8 sampler draws bit-identical too),
   fullcov_sample 0.018, head_stats 0.030 (fit; sums 1.9e-4 of 1e-11 sum|term|),
   fullcov_stats 0.0039 (moments, of 1e-12)
+  mix_em 5.8e-4 with mix_out (the factors' backward error of 1e-4; moments
+  1.4e-5 and total 1.2e-4 of EM_TOL) and 1.2e-4 without (total), ped_mask at
+  +1, +2 and +3 alike; mix_sample 0.0039, comp the checker's, the in-place call
+  (out == pred at +4) the separate output's bits; mix_best_of_k 0.0027,
+  mix_joint_eval 0.0015, mix_kde_nll 5.8e-4 (of tests/mix_eval_ref.py's gate;
+  each of the 8 sampler draws bit-identical too); the sample scores, F = 3 /
+  F = 20 (two workgroups a scene: the workspace's rows at +4), ped_mask at +1,
+  +2 and +3: per-step 0.0022 / 0.0042, fullcov 0.0020 / 0.0036, mix 0.0021 /
+  0.0038 (a pair's column, of tests/scores_ref.py's TOL)
 The wrapper test (views at 4 mod 16 of one padded flat buffer): bit-identical.
 """
 import ctypes
@@ -86,6 +97,9 @@ WEIGHTS = ("Wi", "Wii", "Wv", "bv", "Wr", "Wc", "Wo")
 
 @pytest.fixture
 def lib(gpu):
+    """The library with all three headers' symbols bound (one handle)."""
+    from multimodaltraj_2_amd import mixture, scores
+    assert mixture.load() is _lib.load() and scores.load() is _lib.load()
     return _lib.load()
 
 
@@ -464,6 +478,15 @@ def twice(name, entry, run, cond=None, mask=1):
     base = run(Bufs(entry, False))
     moved = run(Bufs(entry, True, cond, mask))
     compare(name, base, moved)
+    return base
+
+
+def every_mask(name, entry, run):
+    """`twice` with ped_mask at +1, then the minimum launch again with it at +2
+    and +3, each against the same +0 launch."""
+    base = twice(f"{name} mask+1", entry, run, mask=1)
+    for mask in (2, 3):
+        compare(f"{name} mask+{mask}", base, run(Bufs(entry, True, None, mask)))
     return base
 
 
@@ -847,6 +870,9 @@ def test_nri_ops_at_minimum_alignment(lib):
 # ---------------------------------------------------------------------------
 from tests import bestk_ref, calib_ref, fullcov_joint_ref, joint_ref, kde_ref  # noqa: E402
 from tests import fullcov_ref as fr  # noqa: E402
+from tests import mix_eval_ref as me  # noqa: E402
+from tests import mixture_ref as mr  # noqa: E402
+from tests import scores_ref  # noqa: E402
 
 MASK64 = (1 << 64) - 1
 
@@ -863,8 +889,13 @@ def eval_inputs(S=3, F=3, Nmax=7, seed=8400):
     head = draw_head(rng, edge=False)
     head[2] = 0.5 * rng.standard_normal(12)
     chol = (fr.block_factor(head) + np.tril(0.05 * rng.standard_normal((24, 24)), -1)).astype(np.float32)
+    # the mixture: live slots 0, 2, 5 with dead ones between them, NaN in the
+    # dead slots, in floats 1..7 and above the diagonals (its own generators)
+    mix = me.mix_block(0.3, seed)
+    assert list(np.flatnonzero(mix[:, 0])) == [0, 2, 5] and np.isnan(mix[1, 8]) and np.isnan(mix[0, 1])
     return dict(S=S, F=F, Nmax=Nmax, n_active=n_active, n_frames=n_frames, mask=mask, pred=pred, tgt=tgt,
-                head=head, chol=chol, pairs=bestk_ref.pair_mask(S, F, Nmax, n_active, n_frames, mask))
+                head=head, chol=chol, mix=mix,
+                pairs=bestk_ref.pair_mask(S, F, Nmax, n_active, n_frames, mask))
 
 
 def pair_inputs(b, c, hname, harr):
@@ -872,10 +903,11 @@ def pair_inputs(b, c, hname, harr):
             b.put("n_frames", c["n_frames"], np.int32), b.put("ped_mask", c["mask"]), b.put(hname, harr)]
 
 
-HEADS = [("head", ""), ("chol", "fullcov_")]
+HEADS = [("head", ""), ("chol", "fullcov_"), ("mix", "mix_")]
+HEAD_IDS = ["per-step", "fullcov", "mix"]
 
 
-@pytest.mark.parametrize("hname,stem", HEADS, ids=["per-step", "fullcov"])
+@pytest.mark.parametrize("hname,stem", HEADS, ids=HEAD_IDS)
 def test_best_of_k_at_minimum_alignment(lib, hname, stem):
     c = eval_inputs()
     S, F, N, K, seed = c["S"], c["F"], c["Nmax"], 8, 2 ** 32 - 3
@@ -897,8 +929,8 @@ def test_best_of_k_at_minimum_alignment(lib, hname, stem):
     at = offsets_at_minimum(entry)
     assert (at["targets"], at["per_ped"], at["workspace"], at["pred"], at[hname]) == (8, 0, 4, 4, 4)
     o = twice(entry, entry, run)
-    R = (bestk_ref if hname == "head" else fr).best_of_k_ref(c["pred"], c["tgt"], c["n_active"], c[hname], seed,
-                                                             K, c["n_frames"], c["mask"])
+    R = {"head": bestk_ref, "chol": fr, "mix": mr}[hname].best_of_k_ref(
+        c["pred"], c["tgt"], c["n_active"], c[hname], seed, K, c["n_frames"], c["mask"])
     per, out, best = host(o["per_ped"]).astype(np.float64), host(o["out"]).astype(np.float64), host(o["best"])
     m = c["pairs"]
     assert np.all(per[~m] == 0) and np.all(out[:, 6:] == 0)
@@ -910,7 +942,7 @@ def test_best_of_k_at_minimum_alignment(lib, hname, stem):
                    "out": close(out[:, :5], R["out"][:, :5]) / TOL})
 
 
-@pytest.mark.parametrize("hname,stem", HEADS, ids=["per-step", "fullcov"])
+@pytest.mark.parametrize("hname,stem", HEADS, ids=HEAD_IDS)
 def test_joint_eval_at_minimum_alignment(lib, hname, stem):
     c = eval_inputs(seed=8500)
     S, F, N, K, seed, radius = c["S"], c["F"], c["Nmax"], 8, 11, 0.3
@@ -934,7 +966,7 @@ def test_joint_eval_at_minimum_alignment(lib, hname, stem):
     at = offsets_at_minimum(entry)
     assert (at["targets"], at["sums_i"], at["workspace"], at["per_frame_i"]) == (8, 8, 4, 4)
     o = twice(entry, entry, run)
-    R = (joint_ref if hname == "head" else fullcov_joint_ref).joint_eval_ref(
+    R = {"head": joint_ref, "chol": fullcov_joint_ref, "mix": me}[hname].joint_eval_ref(
         c["pred"], c["tgt"], c["n_active"], c[hname], seed, K, radius, c["n_frames"], c["mask"])
     pf, sf = host(o["per_frame_f"]).astype(np.float64), host(o["sums_f"]).astype(np.float64)
     pi, si = host(o["per_frame_i"]).astype(np.int64), host(o["sums_i"])
@@ -950,10 +982,11 @@ def test_joint_eval_at_minimum_alignment(lib, hname, stem):
                    "sums_f": close(sf[:, :2], R["sums_f"][:, :2]) / TOL})
 
 
-@pytest.mark.parametrize("hname,stem", HEADS, ids=["per-step", "fullcov"])
+@pytest.mark.parametrize("hname,stem", HEADS, ids=HEAD_IDS)
 def test_kde_nll_at_minimum_alignment(lib, hname, stem):
     """The float64 checker runs over the device's own K draws (the samplers at
-    +0), held to tests/kde_ref.py's gate as tests/test_kde_nll_gpu.py does;
+    +0), held to tests/kde_ref.py's gate as tests/test_kde_nll_gpu.py does (the
+    mixture head: tests/mix_eval_ref.py's, as tests/test_mix_eval_gpu.py);
     the samplers themselves at their minimum are compared with those draws."""
     c = eval_inputs(seed=8600)
     S, F, N, K, seed, floor = c["S"], c["F"], c["Nmax"], 8, 2 ** 64 - 3, -20.0
@@ -966,8 +999,9 @@ def test_kde_nll_at_minimum_alignment(lib, hname, stem):
         def run(b):
             ins = [b.put("pred", c["pred"]), b.put(hname, c[hname])]
             out = b.out("out", c["pred"].shape)
+            tail = (None, None) if hname == "mix" else (None,)            # the mixture's: comp = NULL
             ok(lib, getattr(lib, sampler)(ctypes.byref(d), ptr(ins[0]), ptr(ins[1]),
-                                          ctypes.c_uint64((seed + k) & MASK64), ptr(out), None))
+                                          ctypes.c_uint64((seed + k) & MASK64), ptr(out), *tail))
             b.ar.check_guards()
             assert all_written(out)
             return dict(out=out)
@@ -989,15 +1023,18 @@ def test_kde_nll_at_minimum_alignment(lib, hname, stem):
     at = offsets_at_minimum(entry)
     assert (at["targets"], at["per_ped"], at["workspace"]) == (8, 0, 4)
     o = twice(entry, entry, run)
-    R = kde_ref.kde_nll_ref(draws, c["tgt"], c["pairs"], floor)
+    if hname == "mix":
+        R, gate = me.kde_nll_ref(draws, c["tgt"], c["pairs"], floor), me.GATE
+    else:
+        R, gate = kde_ref.kde_nll_ref(draws, c["tgt"], c["pairs"], floor), kde_ref.GATE
     per, out = host(o["per_ped"]).astype(np.float64), host(o["out"]).astype(np.float64)
     m, npairs = c["pairs"], R["out"][:, 2]
     assert np.all(per[~m] == 0)
     np.testing.assert_array_equal(out[:, 2], npairs)
     assert np.all(out[:, 4] == K) and np.all(out[:, 5] == floor) and np.all(out[:, 6:] == 0)
-    report(entry, {"per pair": float(np.abs(per[..., :2] - R["per_ped"][..., :2]).max()) / kde_ref.GATE,
+    report(entry, {"per pair": float(np.abs(per[..., :2] - R["per_ped"][..., :2]).max()) / gate,
                    "per scene": float((np.abs(out[:, :2] - R["out"][:, :2]).max(axis=1)
-                                       / (kde_ref.GATE * np.maximum(npairs, 1))).max())})
+                                       / (gate * np.maximum(npairs, 1))).max())})
 
 
 @pytest.mark.parametrize("hname,stem", [("head", "head_"), ("chol", "fullcov_")], ids=["per-step", "fullcov"])
@@ -1070,3 +1107,173 @@ def test_workspace_init_at_minimum_alignment(lib):
     o = twice("workspace_init", "g2k_workspace_init", run)
     assert not host(o["workspace"]).any()
     print("workspace_init: exact")
+
+
+# ---------------------------------------------------------------------------
+# include/g2k_mix.h and include/g2k_scores.h: the EM step, the mixture's
+# sampler and the three heads' sample scores (the mixture's best-of-K, joint
+# evaluation and KDE-NLL are the third case of the head tests above)
+# ---------------------------------------------------------------------------
+def em_inputs():
+    """eval_inputs' scenes (a mask, an empty and a short scene) with targets a
+    few component sigma from pred + b_m, as tests/test_mixture_gpu.py draws
+    them (its 0.05 scale: a component's covariance is then well inside what two
+    float64 evaluations agree on), the three components dealt in turn, and NaN
+    in every non-pair of pred and targets."""
+    from tests.test_mixture_gpu import _block
+    c = dict(eval_inputs(seed=8800))
+    S, F, N = c["S"], c["F"], c["Nmax"]
+    rng = np.random.default_rng(8801)
+    slots = (0, 2, 5)
+    mix = _block(rng, slots)
+    k = np.asarray(slots)[np.arange(S * F * N).reshape(S, F, N) % 3]
+    r = np.empty((S, F, N, 24))
+    for m in slots:
+        Lm = np.tril(np.nan_to_num(mix[m, 32:].reshape(24, 24).astype(np.float64)))
+        r[k == m] = 1.3 * mix[m, 8:32] + rng.standard_normal((int((k == m).sum()), 24)) @ (1.2 * Lm).T
+    pred = c["pred"].copy()
+    tg = np.empty((S, F, N, 12, 2))
+    tg[..., 0] = np.transpose(pred[:, :, :12], (0, 1, 3, 2)) + r[..., 0::2]
+    tg[..., 1] = np.transpose(pred[:, :, 12:], (0, 1, 3, 2)) + r[..., 1::2]
+    tg = np.ascontiguousarray(tg.astype(np.float32))
+    m = c["pairs"]
+    np.transpose(pred, (0, 1, 3, 2))[~m] = np.nan
+    tg[~m] = np.nan
+    c.update(pred=pred, tgt=tg, mix=mix, slots=slots)
+    return c
+
+
+@pytest.mark.parametrize("with_out", [True, False], ids=["mix_out", "e-step-only"])
+def test_mix_em_at_minimum_alignment(lib, with_out):
+    """targets, moments, resp, total and the workspace +8, pred, the block in
+    and out, n_active, n_frames +4, ped_mask +1, +2, +3.  The bounds are
+    tests/test_mixture_gpu.py's (its _check_em_step)."""
+    from tests.test_mixture_gpu import _check_em_step
+    c = em_inputs()
+    S, F, N = c["S"], c["F"], c["Nmax"]
+    entry = "g2k_mix_em_f32"
+    d = dims(S=S, F=F, Nmax=N)
+    nws = int(lib.g2k_mix_em_workspace_bytes(ctypes.byref(d)))
+    assert nws == 8 * (8 * S * F * N + 10 + 8 * 448)
+    R = mr.em_ref(c["pred"], c["tgt"], c["n_active"], c["mix"], c["n_frames"], c["mask"])
+    g = np.sort(R["gamma"], axis=1)
+    assert R["total"][0] == c["pairs"].sum() > 12 and (g[:, -1] - g[:, -2]).min() > 1e-9
+    assert np.all(R["resp"][list(c["slots"]), 0] > 2.0)
+
+    def run(b):
+        ins = pair_inputs(b, c, "mix_in", c["mix"])
+        mo, rs = b.out("moments", (8, 25, 24), torch.float64), b.out("resp", (8, 2), torch.float64)
+        tt, out = b.out("total", (4,), torch.float64), b.out("mix_out", (8, 608))
+        ws = b.out("workspace", (nws,), U8)
+        ok(lib, lib.g2k_mix_em_f32(ctypes.byref(d), *[ptr(t) for t in ins], ptr(mo), ptr(rs), ptr(tt),
+                                   ptr(out) if with_out else None, ptr(ws), nws, None))
+        b.ar.check_guards()
+        assert all_written(mo) and all_written(rs) and all_written(tt)
+        assert all_written(out) if with_out else bool(untouched(out).all())
+        assert np.array_equal(bits(ins[5]).cpu().numpy(), c["mix"].view(np.int32))       # the block: read only
+        return dict(moments=mo, resp=rs, total=tt, mix_out=out)
+
+    at = offsets_at_minimum(entry)
+    assert (at["targets"], at["moments"], at["resp"], at["total"], at["workspace"]) == (8, 8, 8, 8, 8)
+    assert (at["pred"], at["mix_in"], at["mix_out"], at["n_active"], at["ped_mask"]) == (4, 4, 4, 4, 1)
+    name = entry + ("" if with_out else " (mix_out NULL)")
+    o = every_mask(name, entry, run)
+    out = host(o["mix_out"]) if with_out else R["mix_out"]          # NULL: the E-step's outputs only
+    r = _check_em_step(name, host(o["moments"]), host(o["resp"]), host(o["total"]), out, R, list(c["slots"]))
+    if not with_out:
+        r = {k: r[k] for k in ("moments", "resp", "total")}
+    report(name, r)
+
+
+def test_mix_sample_at_minimum_alignment(lib):
+    """pred, mix, out and comp +4; then in place (out == pred) at +4: the bits
+    of the separate output."""
+    c = eval_inputs(seed=8900)
+    S, F, N, seed = c["S"], c["F"], c["Nmax"], 2 ** 64 - 5
+    entry = "g2k_mix_sample_f32"
+    d = dims(S=S, F=F, Nmax=N)
+
+    def run(b):
+        pred, mix = b.put("pred", c["pred"]), b.put("mix", c["mix"])
+        out, comp = b.out("out", c["pred"].shape), b.out("comp", (S, F, N), torch.int32)
+        ok(lib, lib.g2k_mix_sample_f32(ctypes.byref(d), ptr(pred), ptr(mix), ctypes.c_uint64(seed), ptr(out),
+                                       ptr(comp), None))
+        b.ar.check_guards()
+        assert all_written(out) and all_written(comp)
+        assert np.array_equal(host(pred).view(np.int32), c["pred"].view(np.int32))       # read only
+        return dict(out=out, comp=comp)
+
+    def in_place(b):
+        pred, mix = b.put("pred", c["pred"]), b.put("mix", c["mix"])
+        ok(lib, lib.g2k_mix_sample_f32(ctypes.byref(d), ptr(pred), ptr(mix), ctypes.c_uint64(seed), ptr(pred),
+                                       None, None))
+        b.ar.check_guards()
+        return dict(out=pred)
+
+    at = offsets_at_minimum(entry)
+    assert at == dict(pred=4, mix=4, out=4, comp=4)
+    o = twice(entry, entry, run)
+    ip = twice(entry + " in place", entry, in_place)
+    compare(entry + " in place against the separate output", dict(out=o["out"]), ip)
+    ref, rcomp = mr.sample(c["pred"], c["mix"], seed)
+    np.testing.assert_array_equal(host(o["comp"]), rcomp)
+    assert set(np.unique(rcomp)) == {0, 2, 5} and np.all(np.isfinite(host(o["out"])))
+    report(entry, {"draw": close(host(o["out"]), ref) / TOL})
+
+
+SCORE_SAMPLERS = {"head": "g2k_gauss_sample_f32", "chol": "g2k_fullcov_sample_f32", "mix": "g2k_mix_sample_f32"}
+
+
+@pytest.mark.parametrize("F", [3, 20], ids=["f3", "f20-rows"])
+@pytest.mark.parametrize("hname,stem", HEADS, ids=HEAD_IDS)
+def test_sample_scores_at_minimum_alignment(lib, hname, stem, F):
+    """targets +8, per_ped (two float4 stores a pair) +0, the workspace, pred,
+    the head's parameters, out, n_active and n_frames +4, ped_mask +1, +2, +3;
+    K = 5.  F = 3 is one workgroup a scene; F = 20 two (18 frames, then 2), so
+    the workspace at +4 holds the rows that g2k_scores_rows_kernel adds.  The
+    float64 checker runs over the device's own K draws (the head's sampler at
+    +0), held to tests/scores_ref.py's TOL as tests/test_sample_scores_gpu.py
+    does."""
+    c = eval_inputs(F=F, seed=9000)
+    S, N, K, seed = c["S"], c["Nmax"], 5, 2 ** 32 - 2
+    entry = f"g2k_{stem}sample_scores_f32"
+    d = dims(S=S, F=F, Nmax=N)
+    nws = int(lib.g2k_sample_scores_workspace_bytes(ctypes.byref(d)))
+    assert nws == S * F * 32
+    geom = (ctypes.c_int32 * 5)()
+    assert lib.g2k_sample_scores_geometry(ctypes.byref(d), K, geom) == 0
+    assert (geom[2], geom[3]) == ((3, 1) if F == 3 else (18, 2))      # FC, C
+
+    def run(b):
+        ins = pair_inputs(b, c, hname, c[hname])
+        per, out, ws = b.out("per_ped", (S, F, N, 8)), b.out("out", (S, 8)), b.out("workspace", (nws,), U8)
+        ok(lib, getattr(lib, entry)(ctypes.byref(d), *[ptr(t) for t in ins], ctypes.c_uint64(seed), K, ptr(per),
+                                    ptr(out), ptr(ws), nws, None))
+        b.ar.check_guards()
+        assert all_written(per) and all_written(out)
+        return dict(per_ped=per, out=out)
+
+    at = offsets_at_minimum(entry)
+    assert (at["targets"], at["per_ped"], at["workspace"], at["pred"], at[hname], at["out"]) == (8, 0, 4, 4, 4, 4)
+    o = every_mask(f"{entry} F={F}", entry, run)
+
+    def draw(k):
+        ar = Arena("cuda")
+        pred, prm, out = ar.put(c["pred"], "pred"), ar.put(c[hname], hname), ar.alloc(c["pred"].shape, name="out")
+        tail = (None, None) if hname == "mix" else (None,)
+        ok(lib, getattr(lib, SCORE_SAMPLERS[hname])(ctypes.byref(d), ptr(pred), ptr(prm),
+                                                    ctypes.c_uint64((seed + k) & MASK64), ptr(out), *tail))
+        ar.check_guards()
+        return host(out)
+
+    R = scores_ref.sample_scores_ref(np.stack([draw(k) for k in range(K)]), c["tgt"], c["pairs"])
+    per, out = host(o["per_ped"]).astype(np.float64), host(o["out"]).astype(np.float64)
+    m, npairs = c["pairs"], R["out"][:, 7]
+    assert np.all(per[~m] == 0) and np.all(per[..., 7] == 0) and m.sum() > 12
+    np.testing.assert_array_equal(out[:, 7], npairs)
+    gate = lambda ref: scores_ref.TOL * np.maximum(1.0, np.abs(ref))      # noqa: E731
+    report(f"{entry} F={F}", {"per pair": float((np.abs(per[..., :7] - R["per_ped"][..., :7])
+                                                 / gate(R["per_ped"][..., :7])).max()),
+                              "per scene": float((np.abs(out[:, :7] - R["out"][:, :7])
+                                                  / (gate(R["out"][:, :7])
+                                                     * np.maximum(npairs, 1)[:, None])).max())})

@@ -345,3 +345,14 @@ def test_init_from_is_deterministic_and_the_definition():
     assert np.all(got[:3, 0] == np.float32(1 / 3))
     with pytest.raises(ValueError, match="components = 9"):
         mixture.MixtureHead.init_from(st, 9, device="cpu")
+
+
+def test_gpu_em_cases_reach_their_branches():
+    """The inputs of tests/test_mixture_gpu.py's EM cases "outliers", "starved"
+    and "cap" meet the conditions under which they reach the branches they are
+    for (the max-shifted logsumexp, the "too little mass" finish, the
+    256-workgroup cap), and the selector blocks their edges: conditions on the
+    checker alone, held here so that the CPU suite sees a case drift away."""
+    from tests import test_mixture_gpu as tg
+    tg.em_branch_preconditions(log=lambda s: None)
+    tg.selector_edge_preconditions()
