@@ -4,7 +4,8 @@ the build's own: --data_root (Q8), --device, --mode,
 --log_dir, --save_dir, --seed, --use_grid_lstm, --loss, --num_samples,
 --sample_seed, --head_log_sigma, --collision_radius, --fit_head,
 --calibration, --fullcov_head, --mixture_head, --mixture_components,
---mixture_iters, --kde_nll, --kde_floor, --sample_scores."""
+--mixture_iters, --kde_nll, --kde_floor, --sample_scores, --sample_modes,
+--modes_draws, --modes_iters, --miss_radius."""
 import argparse
 
 
@@ -105,6 +106,21 @@ class ArgsParser:
                              '(24-D norm, ADE, FDE), the expected ADE / FDE of a draw, the average '
                              'pairwise displacement and the variogram score of the K draws, of the '
                              'per-step head and, with --fullcov_head / --mixture_head, of those heads')
+    parser.add_argument('--sample_modes', type=int, default=0,
+                        help='--num_samples: M in 1..32 also reduces --modes_draws draws of each head '
+                             'in use to M representative trajectories with probabilities (k-means '
+                             'over the 24-D trajectories of a pedestrian) and reports minADE_M / '
+                             'minFDE_M of the centres, their Brier variants, the inertia and the '
+                             'live clusters (0: off)')
+    parser.add_argument('--modes_draws', type=int, default=256,
+                        help='--sample_modes M: draws clustered per pedestrian, M..256 (seed '
+                             '--sample_seed: the first --num_samples are the best-of-K draws)')
+    parser.add_argument('--modes_iters', type=int, default=10,
+                        help="--sample_modes: iterations of Lloyd's algorithm, 0..64")
+    parser.add_argument('--miss_radius', type=float, default=0.0,
+                        help='--sample_modes: also report the miss rate, the share of pedestrians '
+                             'whose best centre ends farther than this from the target, in the units '
+                             "of the dataset's position columns (0: off)")
     parser.add_argument('--train_scenes', type=int, default=0,
                         help='--mode train: distinct scenes used (0: all of the fold)')
     parser.add_argument('--valid_from_seed', type=int, default=0,

@@ -1,0 +1,495 @@
+// g2k_modes.hip — fused k-means reduction of a probabilistic head's samples to
+// M modes and the scores of the M centres.  ONE kernel,
+// sample_modes_kernel<Head>, instantiated for the per-step head
+// (g2k_sample_modes_f32), the full-covariance head
+// (g2k_fullcov_sample_modes_f32) and the mixture head
+// (g2k_mix_sample_modes_f32); the heads are the policies of g2k_head_draw.h.
+// The C entry points are at the end of this file, declared in
+// include/g2k_modes.h (added after ABI 11: bound by symbol), which holds the
+// definition.  The build's: the reference has no probabilistic head, so PARITY
+// UNPINNED; pinned against tests/modes_ref.py.
+//
+// Everything after the draw is double precision (the definition's: Lloyd's
+// argmin is not reproducible in f32).  The draws themselves stay f32 in LDS,
+// as in g2k_scores.hip, and are widened where they are used.
+//
+// Geometry (modes_geom below): the shape of sample_scores_kernel.  One
+// workgroup of 256 threads per (scene, chunk of FC frames); a pass takes G
+// pairs, lane tid owns (pair tid / K, draw tid % K) and LDS slot tid; G =
+// min(256 / K, 64 / M, 32): the M centres of every pair of the pass are in
+// LDS as doubles, cen[G * M][24] (12 KB at G M = 64, which with the draws'
+// 24 KB and the mixture head's 19 KB stays below 64 KB: two workgroups per
+// CU), and a lane per pair finishes (32).  Per pass:
+//   draw     the lane draws X_k and stores it in its slot           1 barrier
+//   start    the G M 24 centre coordinates, dealt to the lanes, are copied
+//            from the first M slots of their pair                   1 barrier
+//   iters x  assign: the lane keeps X_k in registers and walks its pair's M
+//            centres (ds_read_b128 of two doubles: a broadcast within the
+//            pair's lanes), the lowest m of the smallest d2 goes to asg[tid]
+//            update: item (pair, m, j) walks the pair's K slots in k order,
+//            adds X_k[j] where asg = m, counts, divides       2 barriers each
+//   final    one more assign, which also keeps d2 of the lane's own centre
+//   items    (pair, m): n_m and the centre's A_m, F_m against the target;
+//            (pair): the inertia, the K lanes' d2 in k order        1 barrier
+//   finish   lane tid < G takes pair tid: the two argmins, per_ped and the
+//            lane's eight double sums; all lanes write the pass's centres and
+//            weights, pair index fastest (adjacent lanes, adjacent n)
+// Control flow is uniform: there is no convergence test.
+// Scene sums: every finishing lane's eight doubles go to LDS at the end, eight
+// lanes add the 32 rows in lane order; per-workgroup rows [S * C][8] of doubles
+// in the caller's workspace, then g2k_modes_rows_kernel adds a scene's C rows in
+// chunk order and rounds once; C == 1 rounds and writes out directly.
+#include <math.h>
+
+#include "g2k_common.h"
+#include "g2k_head_draw.h"
+#include "g2k_modes.h"
+
+namespace g2k {
+namespace {
+
+constexpr int kMoThreads = 256;
+constexpr int kMoMaxG = 32;                   // pairs per pass: a finishing lane each
+constexpr int kMoMaxGM = 64;                  // centres per pass: the LDS budget
+constexpr int kMoPitch = kL2;                 // floats per draw in LDS
+constexpr int kMoPasses = 4;                  // passes that a workgroup's frames are sized for
+// xy, cen, dmin, stat {A, F}, cnt, asg, iner, sums
+constexpr int kMoLdsBytes = kMoThreads * kMoPitch * 4 + kMoMaxGM * kL2 * 8 + kMoThreads * 8 +
+                            kMoMaxGM * 2 * 8 + kMoMaxGM * 4 + kMoThreads + kMoMaxG * 8 +
+                            kMoMaxG * 8 * 8;
+
+struct ModesGeom { int G, FC, C; };
+
+inline ModesGeom modes_geom(const g2k_dims& d, int K, int M) {
+  ModesGeom g;
+  g.G = kMoThreads / K;
+  if (g.G > kMoMaxGM / M) g.G = kMoMaxGM / M;
+  if (g.G > kMoMaxG) g.G = kMoMaxG;
+  int fc = (kMoPasses * g.G) / d.Nmax;
+  if (fc > d.F) fc = d.F;
+  if (fc < 1) fc = 1;
+  g.FC = fc;
+  g.C = d.F > 0 ? (d.F + fc - 1) / fc : 1;
+  return g;
+}
+
+// the lane's draw against its pair's M centres: the lowest m of the smallest
+// d2 (j ascending), and that d2
+__device__ __forceinline__ int assign_lane(const float (&x)[kL2], const double* __restrict__ c, int M,
+                                           double& best) {
+  int a = 0;
+  best = 0.0;
+#pragma nounroll
+  for (int m = 0; m < M; ++m) {
+    const double2* c2 = reinterpret_cast<const double2*>(c + m * kL2);
+    double d2 = 0.0;
+#pragma unroll
+    for (int q = 0; q < kL2 / 2; ++q) {
+      const double2 v = c2[q];
+      const double e0 = (double)x[2 * q] - v.x, e1 = (double)x[2 * q + 1] - v.y;
+      d2 += e0 * e0;
+      d2 += e1 * e1;
+    }
+    if (m == 0 || d2 < best) { best = d2; a = m; }
+  }
+  return a;
+}
+
+template <class Head>
+__global__ void __launch_bounds__(kMoThreads) sample_modes_kernel(
+    const float* __restrict__ pred, const float* __restrict__ targets,
+    const int32_t* __restrict__ n_active, const int32_t* __restrict__ n_frames,
+    const uint8_t* __restrict__ ped_mask, const float* __restrict__ head_params, int F, int Nmax,
+    int FC, int C, int G, int K, int M, int iters, uint32_t seed_lo, uint32_t seed_hi,
+    int shared_targets, double miss_radius, float* __restrict__ per_ped, float* __restrict__ centres,
+    float* __restrict__ weights, float* __restrict__ out, double* __restrict__ rows) {
+  __shared__ typename Head::Lds hlds;
+  __shared__ __attribute__((aligned(16))) float xy[kMoThreads * kMoPitch];
+  __shared__ __attribute__((aligned(16))) double cen[kMoMaxGM * kL2];
+  __shared__ double dmin[kMoThreads];
+  __shared__ double statA[kMoMaxGM], statF[kMoMaxGM];
+  __shared__ int cnt[kMoMaxGM];
+  __shared__ uint8_t asg[kMoThreads];
+  __shared__ double iner[kMoMaxG];
+  __shared__ double sums[kMoMaxG][8];
+  const int tid = threadIdx.x;
+  const int s = blockIdx.x / C, c = blockIdx.x - s * C;
+  const int f0 = c * FC;
+  const int fcn = min(FC, F - f0);                         // frames of this chunk (0 when F == 0)
+  const int nact = clampi(n_active[s], 0, Nmax);
+  const int nf = n_frames ? clampi(n_frames[s], 0, F) : F;
+  const int nfc = clampi(nf - f0, 0, fcn);                 // ... of them below n_frames
+  const uint8_t* mask = ped_mask ? ped_mask + (size_t)s * Nmax : nullptr;
+
+  Head::template stage<kMoThreads>(head_params, hlds, tid);
+  // non-pairs: zeros in per_ped, centres and weights
+  if (per_ped || centres || weights) {
+    const int rows_c = centres ? M * kL2 : 0, rows_w = weights ? M : 0, rows_p = per_ped ? 1 : 0;
+    const int nrows = rows_c + rows_w + rows_p;
+    for (int idx = tid; idx < fcn * nrows * Nmax; idx += kMoThreads) {
+      const int n = idx % Nmax;
+      const int r = (idx / Nmax) % nrows, fl = idx / (Nmax * nrows);
+      const bool pair = fl < nfc && n < nact && (mask ? mask[n] != 0 : true);
+      if (pair) continue;
+      const size_t sf = (size_t)s * F + f0 + fl;
+      if (r < rows_c) {
+        centres[(sf * M * kL2 + r) * Nmax + n] = 0.f;
+      } else if (r < rows_c + rows_w) {
+        weights[(sf * M + (r - rows_c)) * Nmax + n] = 0.f;
+      } else {
+        float4* o = reinterpret_cast<float4*>(per_ped) + (sf * Nmax + n) * 2;
+        o[0] = make_float4(0.f, 0.f, 0.f, 0.f);
+        o[1] = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    }
+  }
+  __syncthreads();
+  Head head;
+  head.bind(hlds);
+
+  const int g = tid / K, k = tid - g * K;                  // this lane's pair of the pass and its draw
+  const int npairs = nfc * nact;
+  const uint32_t lo = seed_lo + (uint32_t)k;               // (seed + k) mod 2^64
+  const uint32_t hi = seed_hi + (lo < seed_lo ? 1u : 0u);
+  const double dK = (double)K;                             // w_m = n_m / K, the inertia = sum / K: divided, as defined
+  double acc[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) acc[i] = 0.0;
+#pragma nounroll
+  for (int base = 0; base < npairs; base += G) {           // uniform trip count
+    const int gp = min(G, npairs - base);                  // pairs of this pass
+    // ---- draw ----
+    const int p = base + g;
+    const bool valid = g < gp;
+    const int fl = valid ? p / nact : 0, n = valid ? p - fl * nact : 0;
+    const bool on = valid && (mask ? mask[n] != 0 : true);
+    float x[kL2];
+    if (on) {
+      const size_t sf = (size_t)s * F + f0 + fl;
+      const int64_t e0 = (int64_t)(sf * kL) * Nmax + n;    // element of step 0
+      float mu[kL2], tg[kL2];
+      load_mu_tg(true, pred, targets, sf, shared_targets ? (size_t)s : sf, n, Nmax, mu, tg);
+      head.draw(lo, hi, e0, Nmax, mu, [&](int t, float px, float py) {
+        x[2 * t] = px;
+        x[2 * t + 1] = py;
+      });
+      float4* o = reinterpret_cast<float4*>(xy + tid * kMoPitch);
+#pragma unroll
+      for (int q = 0; q < kL2 / 4; ++q)
+        o[q] = make_float4(x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < kL2; ++i) x[i] = 0.f;
+    }
+    __syncthreads();
+    // ---- start: c_m = X_m ----
+    const int ncoord = gp * M * kL2;
+    for (int idx = tid; idx < ncoord; idx += kMoThreads) {
+      const int gm = idx / kL2, j = idx - gm * kL2;
+      const int gi = gm / M, m = gm - gi * M;
+      const int pp = base + gi;
+      const int n2 = pp % nact;
+      double v = 0.0;
+      if (mask ? mask[n2] != 0 : true) v = (double)xy[(gi * K + m) * kMoPitch + j];
+      cen[idx] = v;
+    }
+    __syncthreads();
+    // ---- Lloyd ----
+    const double* mine = cen + (valid ? g : 0) * M * kL2;
+    double best = 0.0;
+#pragma nounroll
+    for (int it = 0; it < iters; ++it) {
+      if (on) asg[tid] = (uint8_t)assign_lane(x, mine, M, best);
+      __syncthreads();
+      for (int idx = tid; idx < ncoord; idx += kMoThreads) {
+        const int gm = idx / kL2, j = idx - gm * kL2;
+        const int gi = gm / M, m = gm - gi * M;
+        const int pp = base + gi;
+        const int n2 = pp % nact;
+        if (mask ? mask[n2] != 0 : true) {
+          const int slot0 = gi * K;
+          double sum = 0.0;
+          int nm = 0;
+          // both reads unconditional and the term selected (adding 0.0 leaves the
+          // sum as it is): no branch in the walk, the reads of several slots in flight
+#pragma unroll 8
+          for (int kk = 0; kk < K; ++kk) {
+            const bool in = asg[slot0 + kk] == m;
+            const double v = (double)xy[(slot0 + kk) * kMoPitch + j];
+            sum += in ? v : 0.0;
+            nm += in ? 1 : 0;
+          }
+          if (nm > 0) cen[idx] = sum / (double)nm;       // an empty cluster keeps its centre
+        }
+      }
+      __syncthreads();
+    }
+    // ---- final assignment ----
+    if (on) {
+      asg[tid] = (uint8_t)assign_lane(x, mine, M, best);
+      dmin[tid] = best;
+    }
+    __syncthreads();
+    // ---- items: (pair, m) and (pair) ----
+    for (int idx = tid; idx < gp * (M + 1); idx += kMoThreads) {
+      const int gi = idx / (M + 1), m = idx - gi * (M + 1);
+      const int pp = base + gi;
+      const int fl2 = pp / nact, n2 = pp - fl2 * nact;
+      if (mask ? mask[n2] != 0 : true) {
+        const int slot0 = gi * K;
+        if (m < M) {
+          int nm = 0;
+#pragma nounroll
+          for (int kk = 0; kk < K; ++kk) nm += asg[slot0 + kk] == m ? 1 : 0;
+          const size_t tf2 = shared_targets ? (size_t)s : (size_t)s * F + f0 + fl2;
+          const float2* t2 = reinterpret_cast<const float2*>(targets) + (tf2 * Nmax + n2) * kL;
+          const double* cm = cen + (gi * M + m) * kL2;
+          double a = 0.0, f = 0.0;
+#pragma unroll
+          for (int t = 0; t < kL; ++t) {
+            const float2 y = t2[t];
+            const double dx = cm[2 * t] - (double)y.x, dy = cm[2 * t + 1] - (double)y.y;
+            f = sqrt(dx * dx + dy * dy);
+            a += f;
+          }
+          statA[gi * M + m] = a / 12.0;
+          statF[gi * M + m] = f;
+          cnt[gi * M + m] = nm;
+        } else {
+          double sum = 0.0;
+#pragma nounroll
+          for (int kk = 0; kk < K; ++kk) sum += dmin[slot0 + kk];
+          iner[gi] = sum / dK;
+        }
+      }
+    }
+    __syncthreads();
+    // ---- finish: lane tid < gp takes pair base + tid
+    if (tid < gp) {
+      const int pp = base + tid;
+      const int fl3 = pp / nact, n3 = pp - fl3 * nact;
+      if (mask ? mask[n3] != 0 : true) {
+        double cA = statA[tid * M], cF = statF[tid * M];
+        int mA = 0, mF = 0, live = 0;
+#pragma nounroll
+        for (int m = 0; m < M; ++m) {
+          const double a = statA[tid * M + m], f = statF[tid * M + m];
+          if (a < cA) { cA = a; mA = m; }
+          if (f < cF) { cF = f; mF = m; }
+          live += cnt[tid * M + m] > 0 ? 1 : 0;
+        }
+        const double wA = (double)cnt[tid * M + mA] / dK, wF = (double)cnt[tid * M + mF] / dK;
+        const double in = iner[tid];
+        if (per_ped) {
+          const size_t sf = (size_t)s * F + f0 + fl3;
+          float4* o = reinterpret_cast<float4*>(per_ped) + (sf * Nmax + n3) * 2;
+          o[0] = make_float4((float)cA, (float)cF, (float)mA, (float)mF);
+          o[1] = make_float4((float)wA, (float)wF, (float)in, (float)live);
+        }
+        acc[0] += cA;
+        acc[1] += cF;
+        acc[2] += (1.0 - wA) * (1.0 - wA);
+        acc[3] += (1.0 - wF) * (1.0 - wF);
+        acc[4] += cF > miss_radius ? 1.0 : 0.0;
+        acc[5] += in;
+        acc[6] += (double)live;
+        acc[7] += 1.0;
+      }
+    }
+    // the pass's centres and weights: pair index fastest
+    if (centres) {
+      for (int idx = tid; idx < ncoord; idx += kMoThreads) {
+        const int gi = idx % gp, r = idx / gp;             // r = m * 24 + row
+        const int m = r / kL2, row = r - m * kL2;
+        const int pp = base + gi;
+        const int fl4 = pp / nact, n4 = pp - fl4 * nact;
+        if (mask ? mask[n4] != 0 : true) {
+          const size_t sf = (size_t)s * F + f0 + fl4;
+          const int j = row < kL ? 2 * row : 2 * (row - kL) + 1;   // pred's rows: x then y
+          centres[((sf * M + m) * kL2 + row) * Nmax + n4] = (float)cen[(gi * M + m) * kL2 + j];
+        }
+      }
+    }
+    if (weights) {
+      for (int idx = tid; idx < gp * M; idx += kMoThreads) {
+        const int gi = idx % gp, m = idx / gp;
+        const int pp = base + gi;
+        const int fl4 = pp / nact, n4 = pp - fl4 * nact;
+        if (mask ? mask[n4] != 0 : true) {
+          const size_t sf = (size_t)s * F + f0 + fl4;
+          weights[(sf * M + m) * Nmax + n4] = (float)((double)cnt[gi * M + m] / dK);
+        }
+      }
+    }
+    // no barrier here: the next pass's draw writes xy, which no lane reads past
+    // the items' barrier; cen, cnt and the statistics are next written behind
+    // the next pass's first barrier
+  }
+  // the workgroup's row: the finishing lanes' sums in lane order
+  if (tid < kMoMaxG) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) sums[tid][i] = acc[i];
+  }
+  __syncthreads();
+  if (tid < 8) {
+    double v = 0.0;
+#pragma nounroll
+    for (int l = 0; l < kMoMaxG; ++l) v += sums[l][tid];
+    if (rows) rows[(size_t)blockIdx.x * 8 + tid] = v;
+    else out[(size_t)blockIdx.x * 8 + tid] = (float)v;
+  }
+}
+
+// out[s][i] = the sum over the scene's C chunk rows, in chunk order, rounded once
+__global__ void __launch_bounds__(256) g2k_modes_rows_kernel(const double* __restrict__ rows, int S,
+                                                             int C, float* __restrict__ out) {
+  const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (id >= (int64_t)S * 8) return;
+  const int64_t s = id >> 3;
+  const int i = (int)(id & 7);
+  double v = 0.0;
+  for (int c = 0; c < C; ++c) v += rows[((size_t)s * C + c) * 8 + i];
+  out[id] = (float)v;
+}
+
+template <class Head>
+int sample_modes_launch(const g2k_dims* d, const float* pred, const float* targets,
+                        const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                        const float* head_params, uint64_t seed, int K, int M, int iters,
+                        float miss_radius, float* per_ped, float* centres, float* weights, float* out,
+                        double* rows, hipStream_t st) {
+  const ModesGeom g = modes_geom(*d, K, M);
+  const int64_t wgs = (int64_t)d->S * g.C;
+  if (wgs > 0x7fffffff)
+    return set_err(G2K_EINVAL, "%ssample_modes: %lld workgroups", Head::kPrefix, (long long)wgs);
+  hipLaunchKernelGGL(sample_modes_kernel<Head>, dim3((unsigned)wgs), dim3(kMoThreads), 0, st, pred,
+                     targets, n_active, n_frames, ped_mask, head_params, d->F, d->Nmax, g.FC, g.C, g.G,
+                     K, M, iters, (uint32_t)seed, (uint32_t)(seed >> 32),
+                     (d->flags & G2K_STEP_TARGETS_SHARED) ? 1 : 0, (double)miss_radius, per_ped,
+                     centres, weights, out, g.C == 1 ? (double*)nullptr : rows);
+  int rc = check_launch("sample_modes_kernel");
+  if (rc || g.C == 1) return rc;
+  hipLaunchKernelGGL(g2k_modes_rows_kernel, dim3((unsigned)(((int64_t)d->S * 8 + 255) / 256)),
+                     dim3(256), 0, st, rows, d->S, g.C, out);
+  return check_launch("g2k_modes_rows_kernel");
+}
+
+bool modes_dims_ok(const g2k_dims* d) {
+  return d->S >= 0 && d->F >= 0 && d->Nmax >= 1 && d->Nmax <= kMaxN;
+}
+
+// one row [8] of doubles per (scene, chunk); FC >= 1 frame per chunk, so at most F chunks
+int64_t modes_ws_bytes(const g2k_dims* d) {
+  return (int64_t)d->S * (d->F > 1 ? d->F : 1) * 8 * 8;
+}
+
+int modes_params_ok(int32_t K, int32_t M) {
+  if (M < 1 || M > G2K_MODES_MMAX) return set_err(G2K_EINVAL, "M=%d (1..%d)", M, G2K_MODES_MMAX);
+  if (K < M || K > G2K_MODES_KMAX)
+    return set_err(G2K_EINVAL, "K=%d (M=%d..%d)", K, M, G2K_MODES_KMAX);
+  return G2K_OK;
+}
+
+// the argument checks, before any HIP call; G2K_OK with S > 0: launch
+int modes_validate(const char* name, const g2k_dims* d, const void* pred, const void* targets,
+                   const void* n_active, const void* head, int32_t K, int32_t M, int32_t iters,
+                   float miss_radius, const void* per_ped, const void* out, const void* workspace,
+                   int64_t workspace_bytes) {
+  if (!d) return set_err(G2K_EINVAL, "dims is NULL");
+  if (d->flags & ~G2K_STEP_TARGETS_SHARED)
+    return set_err(G2K_EUNSUPPORTED, "%s: flags %d (0 or G2K_STEP_TARGETS_SHARED)", name, d->flags);
+  if (!modes_dims_ok(d)) return set_err(G2K_EINVAL, "S=%d F=%d Nmax=%d", d->S, d->F, d->Nmax);
+  if (const int rc = modes_params_ok(K, M)) return rc;
+  if (iters < 0 || iters > G2K_MODES_ITERS_MAX)
+    return set_err(G2K_EINVAL, "iters=%d (0..%d)", iters, G2K_MODES_ITERS_MAX);
+  if (!(miss_radius >= 0.f) || !isfinite(miss_radius))
+    return set_err(G2K_EINVAL, "miss_radius=%g (finite, >= 0)", (double)miss_radius);
+  if (!pred || !targets || !n_active || !head || !out)
+    return set_err(G2K_EINVAL, "a required buffer pointer is NULL");
+  if (((uintptr_t)targets) & 7) return set_err(G2K_EINVAL, "targets must be 8-byte aligned");
+  if (((uintptr_t)per_ped) & 15) return set_err(G2K_EINVAL, "per_ped must be 16-byte aligned");
+  if (workspace && (((uintptr_t)workspace) & 7))
+    return set_err(G2K_EINVAL, "workspace must be 8-byte aligned");
+  const int64_t need = modes_ws_bytes(d);
+  if (d->S > 0 && (!workspace || workspace_bytes < need))
+    return set_err(G2K_EINVAL, "workspace of %lld bytes needed (got %lld)", (long long)need,
+                   (long long)workspace_bytes);
+  return G2K_OK;
+}
+
+template <class Head>
+int sample_modes(const char* name, const g2k_dims* d, const float* pred, const float* targets,
+                 const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                 const float* head, uint64_t seed, int32_t K, int32_t M, int32_t iters,
+                 float miss_radius, float* per_ped, float* centres, float* weights, float* out,
+                 void* workspace, int64_t workspace_bytes, void* stream) {
+  const int rc = modes_validate(name, d, pred, targets, n_active, head, K, M, iters, miss_radius,
+                                per_ped, out, workspace, workspace_bytes);
+  if (rc || d->S == 0) return rc;
+  return sample_modes_launch<Head>(d, pred, targets, n_active, n_frames, ped_mask, head, seed, K, M,
+                                   iters, miss_radius, per_ped, centres, weights, out,
+                                   static_cast<double*>(workspace), (hipStream_t)stream);
+}
+
+}  // namespace
+}  // namespace g2k
+
+using namespace g2k;
+
+extern "C" {
+
+int64_t g2k_sample_modes_workspace_bytes(const g2k_dims* d) {
+  if (!d || !modes_dims_ok(d)) return -1;
+  return modes_ws_bytes(d);
+}
+
+// the launch geometry (modes_geom: host arithmetic, no HIP call), as the
+// launcher works it out
+int g2k_sample_modes_geometry(const g2k_dims* d, int32_t K, int32_t M, int32_t* out) {
+  if (!d) return set_err(G2K_EINVAL, "dims is NULL");
+  if (!modes_dims_ok(d)) return set_err(G2K_EINVAL, "S=%d F=%d Nmax=%d", d->S, d->F, d->Nmax);
+  if (const int rc = modes_params_ok(K, M)) return rc;
+  if (!out) return set_err(G2K_EINVAL, "out is NULL");
+  const ModesGeom g = modes_geom(*d, K, M);
+  out[G2K_MODES_GEOM_G] = g.G;
+  out[G2K_MODES_GEOM_LANES] = K;
+  out[G2K_MODES_GEOM_FC] = g.FC;
+  out[G2K_MODES_GEOM_C] = g.C;
+  out[G2K_MODES_GEOM_LDS_BYTES] = kMoLdsBytes;
+  return G2K_OK;
+}
+
+int g2k_sample_modes_f32(const g2k_dims* d, const float* pred, const float* targets,
+                         const int32_t* n_active, const int32_t* n_frames,
+                         const uint8_t* ped_mask, const float* head, uint64_t seed, int32_t K,
+                         int32_t M, int32_t iters, float miss_radius, float* per_ped,
+                         float* centres, float* weights, float* out, void* workspace,
+                         int64_t workspace_bytes, void* stream) {
+  return sample_modes<PerStepHead>("sample_modes", d, pred, targets, n_active, n_frames, ped_mask,
+                                   head, seed, K, M, iters, miss_radius, per_ped, centres, weights,
+                                   out, workspace, workspace_bytes, stream);
+}
+
+int g2k_fullcov_sample_modes_f32(const g2k_dims* d, const float* pred, const float* targets,
+                                 const int32_t* n_active, const int32_t* n_frames,
+                                 const uint8_t* ped_mask, const float* chol, uint64_t seed,
+                                 int32_t K, int32_t M, int32_t iters, float miss_radius,
+                                 float* per_ped, float* centres, float* weights, float* out,
+                                 void* workspace, int64_t workspace_bytes, void* stream) {
+  return sample_modes<FullCovHead>("fullcov_sample_modes", d, pred, targets, n_active, n_frames,
+                                   ped_mask, chol, seed, K, M, iters, miss_radius, per_ped, centres,
+                                   weights, out, workspace, workspace_bytes, stream);
+}
+
+int g2k_mix_sample_modes_f32(const g2k_dims* d, const float* pred, const float* targets,
+                             const int32_t* n_active, const int32_t* n_frames,
+                             const uint8_t* ped_mask, const float* mix, uint64_t seed, int32_t K,
+                             int32_t M, int32_t iters, float miss_radius, float* per_ped,
+                             float* centres, float* weights, float* out, void* workspace,
+                             int64_t workspace_bytes, void* stream) {
+  return sample_modes<MixHead>("mix_sample_modes", d, pred, targets, n_active, n_frames, ped_mask,
+                               mix, seed, K, M, iters, miss_radius, per_ped, centres, weights, out,
+                               workspace, workspace_bytes, stream);
+}
+
+}  // extern "C"

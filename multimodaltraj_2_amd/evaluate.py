@@ -58,7 +58,16 @@ launch per head (csrc/g2k_scores.hip; SCORE_FIGURES): the fair energy score with
 the 24-D norm (strictly proper for the joint law of the 12 steps), with the ADE
 and the FDE (marginals only), the expected ADE / FDE of a draw, the average
 pairwise displacement and the variogram score of order 1/2, which is the one
-that sees whether a draw zig-zags.  The units caveat above holds for a pooled fit too: eth_hotel
+that sees whether a draw zig-zags.  --sample_modes M (1 <= M <= 32) reduces
+--modes_draws draws (default 256, seed --sample_seed: the first --num_samples
+of them are the best-of-K call's own) of each head in use to M representative
+trajectories with probabilities, one g2k_sample_modes_f32 launch per head
+(csrc/g2k_modes.hip: --modes_iters rounds of Lloyd's algorithm in double
+precision), and reports MODES_FIGURES: minADE_M / minFDE_M of the centres,
+their Brier variants with the clusters' weights, the inertia and the number of
+live clusters, and with --miss_radius R > 0 (the dataset's own units, as
+--collision_radius) the share of pairs whose best centre ends farther than R
+from the target.  The units caveat above holds for a pooled fit too: eth_hotel
 is normalised, the UCY sets are world coordinates, so a fold that mixes them
 fits one width to both.  The build's: the reference has no probabilistic head
 (SURVEY.md §8(f) row 4), so these figures have no reference counterpart.
@@ -91,6 +100,10 @@ MIX_KDE_FIGURES = tuple("mix_" + k for k in KDE_FIGURES)
 SCORE_FIGURES = ("es_traj", "es_ade", "es_fde", "mean_ade", "mean_fde", "apd", "vs")
 FULLCOV_SCORE_FIGURES = tuple("fullcov_" + k for k in SCORE_FIGURES)
 MIX_SCORE_FIGURES = tuple("mix_" + k for k in SCORE_FIGURES)
+MODES_FIGURES = ("modes_min_ade", "modes_min_fde", "modes_brier_ade", "modes_brier_fde", "modes_inertia",
+                 "modes_live")
+FULLCOV_MODES_FIGURES = tuple("fullcov_" + k for k in MODES_FIGURES)
+MIX_MODES_FIGURES = tuple("mix_" + k for k in MODES_FIGURES)
 
 
 def calib_figures(hs):
@@ -144,6 +157,30 @@ def _score_line(name, K, dataset, res, prefix=""):
             f"{v['es_traj']:.6g} ADE {v['es_ade']:.6g} FDE {v['es_fde']:.6g}, expected ADE / FDE of a "
             f"draw {v['mean_ade']:.6g} / {v['mean_fde']:.6g}, APD {v['apd']:.6g}, variogram score "
             f"{v['vs']:.6g}")
+
+
+def modes_figures(sm, prefix=""):
+    """MODES_FIGURES (``prefix`` "fullcov_": FULLCOV_MODES_FIGURES, "mix_":
+    MIX_MODES_FIGURES) of a modes.SampleModes, and after them
+    ``modes_miss_rate`` when it was taken with a miss radius > 0."""
+    fig = {prefix + k: getattr(sm, k[len("modes_"):]) for k in MODES_FIGURES}
+    if sm.miss_radius > 0:
+        fig[prefix + "modes_miss_rate"] = sm.miss_rate
+    return fig
+
+
+def _modes_line(name, sm, K, dataset, res, prefix=""):
+    """The log line of one head's MODES_FIGURES, next to that head's minADE_K."""
+    v = {k: res[prefix + k] for k in MODES_FIGURES}
+    line = (f"{name} on dataset {dataset}: {sm.modes} centres of {sm.k} draws after {sm.iters} "
+            f"iterations, minADE_{sm.modes} {v['modes_min_ade']:.6g} minFDE_{sm.modes} "
+            f"{v['modes_min_fde']:.6g} (minADE_{K} / minFDE_{K} of the {K} raw draws "
+            f"{res[prefix + 'min_ade']:.6g} / {res[prefix + 'min_fde']:.6g}), Brier "
+            f"{v['modes_brier_ade']:.6g} / {v['modes_brier_fde']:.6g}, inertia "
+            f"{v['modes_inertia']:.6g}, live centres {v['modes_live']:.4g}")
+    if sm.miss_radius > 0:
+        line += f", miss rate at {sm.miss_radius:g} {res[prefix + 'modes_miss_rate']:.4f}"
+    return line
 
 
 def mixture_figures(mx, bk, st, fit):
@@ -225,7 +262,14 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
     and seed) after the per-step head's other figures, and FULLCOV_SCORE_FIGURES
     / MIX_SCORE_FIGURES at the end of those heads' blocks, a log line each
     (``keep["scores"]``, ``keep["fullcov"]["scores"]``,
-    ``keep["mixture"]["scores"]``).
+    ``keep["mixture"]["scores"]``).  --sample_modes M (1..32) adds
+    MODES_FIGURES (and ``modes_miss_rate`` with --miss_radius > 0) from one
+    GaussianHead.sample_modes launch (csrc/g2k_modes.hip; --modes_draws draws,
+    --modes_iters iterations, seed --sample_seed) directly after the per-step
+    head's score figures, and FULLCOV_MODES_FIGURES / MIX_MODES_FIGURES after
+    those heads' score figures, a log line each that puts minADE_M of the
+    centres next to that head's minADE_K (``keep["modes"]``,
+    ``keep["fullcov"]["modes"]``, ``keep["mixture"]["modes"]``).
     ``keep`` (a dict)
     receives the plan, the predictions, the head and the kernels' outputs for
     a caller that checks them."""
@@ -237,6 +281,19 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
     want_scores = bool(getattr(args, "sample_scores", 0))
     if want_scores and not 2 <= K <= 256:
         raise ValueError("--sample_scores 1 needs --num_samples K with 2 <= K <= 256")
+    n_modes = int(getattr(args, "sample_modes", 0) or 0)
+    if n_modes:
+        if not 1 <= n_modes <= 32:
+            raise ValueError("--sample_modes M: 0 (off) or 1 <= M <= 32")
+        modes_draws = int(getattr(args, "modes_draws", 256))
+        if not n_modes <= modes_draws <= 256:
+            raise ValueError("--modes_draws must be in M..256 (M = --sample_modes)")
+        modes_iters = int(getattr(args, "modes_iters", 10))
+        if not 0 <= modes_iters <= 64:
+            raise ValueError("--modes_iters must be in 0..64")
+        miss_radius = float(getattr(args, "miss_radius", 0.0) or 0.0)
+        if not (np.isfinite(miss_radius) and miss_radius >= 0):
+            raise ValueError("--miss_radius must be finite and >= 0")
     fit_mode = getattr(args, "fit_head", "off") or "off"
     calibrate = bool(getattr(args, "calibration", 0)) or fit_mode != "off"
     plan = left_out_plan(args, params.nmax)
@@ -306,8 +363,15 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                                   n_frames=one, ped_mask=t["ped_mask"], want_per_ped=keep is not None)
         res.update(score_figures(scores))
         log(_score_line("sample scores", K, args.leaveDataset, res))
+    modes = None
+    if n_modes:
+        modes_kw = dict(iters=modes_iters, seed=args.sample_seed, miss_radius=miss_radius, n_frames=one,
+                        ped_mask=t["ped_mask"], want_per_ped=keep is not None)
+        modes = gh.sample_modes(out.pred, t["targets"], t["n_active"], modes_draws, n_modes, **modes_kw)
+        res.update(modes_figures(modes))
+        log(_modes_line("sample modes", modes, K, args.leaveDataset, res))
     fc_mode = getattr(args, "fullcov_head", "off") or "off"
-    fc = fc_st = fc_bk = fc_joint = fc_kde = fc_scores = None
+    fc = fc_st = fc_bk = fc_joint = fc_kde = fc_scores = fc_modes = None
     if fc_mode != "off":
         from .fullcov import FullCovHead
         fc = FullCovHead(device=device)
@@ -359,8 +423,14 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                                          want_per_ped=keep is not None)
             res.update(score_figures(fc_scores, "fullcov_"))
             log(_score_line("full-covariance sample scores", K, args.leaveDataset, res, "fullcov_"))
+        if n_modes:
+            fc_modes = fc.sample_modes(out.pred, t["targets"], t["n_active"], modes_draws, n_modes,
+                                       **modes_kw)
+            res.update(modes_figures(fc_modes, "fullcov_"))
+            log(_modes_line("full-covariance sample modes", fc_modes, K, args.leaveDataset, res,
+                            "fullcov_"))
     mx_mode = getattr(args, "mixture_head", "off") or "off"
-    mx = mx_fit = mx_st = mx_bk = mx_joint = mx_kde = mx_scores = None
+    mx = mx_fit = mx_st = mx_bk = mx_joint = mx_kde = mx_scores = mx_modes = None
     if mx_mode != "off":
         from .mixture import MixtureHead
         mx = MixtureHead(components=int(getattr(args, "mixture_components", 3)), device=device)
@@ -413,6 +483,11 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                                          want_per_ped=keep is not None)
             res.update(score_figures(mx_scores, "mix_"))
             log(_score_line("mixture sample scores", K, args.leaveDataset, res, "mix_"))
+        if n_modes:
+            mx_modes = mx.sample_modes(out.pred, t["targets"], t["n_active"], modes_draws, n_modes,
+                                       **modes_kw)
+            res.update(modes_figures(mx_modes, "mix_"))
+            log(_modes_line("mixture sample modes", mx_modes, K, args.leaveDataset, res, "mix_"))
     if keep is not None:
         keep.update(plan=plan, pred=out.pred, head=gh.head, out=bk, n_frames=np.ones(S, np.int32),
                     joint=joint)
@@ -424,12 +499,16 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                 keep["mixture"]["kde"] = mx_kde
             if mx_scores is not None:
                 keep["mixture"]["scores"] = mx_scores
+            if mx_modes is not None:
+                keep["mixture"]["modes"] = mx_modes
         if calibrate:
             keep.update(calib=calib, fitted=fitted)
         if kde is not None:
             keep.update(kde=kde)
         if scores is not None:
             keep.update(scores=scores)
+        if modes is not None:
+            keep.update(modes=modes)
         if fc is not None:
             keep.update(fullcov=dict(stats=fc_st, out=fc_bk, fitted=ffit), fullcov_chol=fc.chol)
             if fc_joint is not None:
@@ -438,6 +517,8 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                 keep["fullcov"]["kde"] = fc_kde
             if fc_scores is not None:
                 keep["fullcov"]["scores"] = fc_scores
+            if fc_modes is not None:
+                keep["fullcov"]["modes"] = fc_modes
     return res
 
 

@@ -311,6 +311,21 @@ class FullCovHead:
         return _sample_scores("g2k_fullcov_sample_scores_f32", self.chol, d, pred, targets, n_active,
                               k, seed, n_frames, ped_mask, want_per_ped, stream)
 
+    def sample_modes(self, pred, targets, n_active, k, modes, iters=10, seed=0, *, miss_radius=0.0,
+                     n_frames=None, ped_mask=None, want_per_ped=True, want_centres=False,
+                     targets_shared=False, stream=None):
+        """K-means reduction to ``modes`` centres in one launch
+        (g2k_fullcov_sample_modes_f32): GaussianHead.sample_modes over this
+        head's correlated draws ``sample(pred, seed + i)``, i < k ->
+        modes.SampleModes."""
+        from .modes import _sample_modes
+        d = self._dims(pred)
+        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
+        self._check_chol(pred.device)
+        return _sample_modes("g2k_fullcov_sample_modes_f32", self.chol, d, pred, targets, n_active, k,
+                             modes, iters, seed, miss_radius, n_frames, ped_mask, want_per_ped,
+                             want_centres, stream)
+
     def joint_eval(self, pred, targets, n_active, k, radius, seed=0, *, n_frames=None, ped_mask=None,
                    targets_shared=False, want_per_frame=True, stream=None):
         """Joint best-of-K evaluation in one launch (g2k_fullcov_joint_eval_f32):

@@ -445,6 +445,21 @@ class GaussianHead:
         return _sample_scores("g2k_sample_scores_f32", self.head, d, pred, targets, n_active, k, seed,
                               n_frames, ped_mask, want_per_ped, stream)
 
+    def sample_modes(self, pred, targets, n_active, k, modes, iters=10, seed=0, *, miss_radius=0.0,
+                     n_frames=None, ped_mask=None, want_per_ped=True, want_centres=False,
+                     targets_shared=False, stream=None):
+        """K-means reduction of the K draws ``sample(pred, seed + i)``, i < k,
+        to ``modes`` centres with probabilities and the centres' scores, in one
+        launch (g2k_sample_modes_f32, csrc/g2k_modes.hip) -> modes.SampleModes.
+        modes in 1..32, k in modes..256, iters in 0..64."""
+        from .modes import _sample_modes
+        d = self._dims(pred)
+        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
+        _check_dev("head", self.head, pred.device, torch.float32)
+        return _sample_modes("g2k_sample_modes_f32", self.head, d, pred, targets, n_active, k, modes,
+                             iters, seed, miss_radius, n_frames, ped_mask, want_per_ped, want_centres,
+                             stream)
+
     def joint_eval(self, pred, targets, n_active, k, radius, seed=0, *, n_frames=None, ped_mask=None,
                    targets_shared=False, want_per_frame=True, stream=None):
         """Joint best-of-K evaluation in one launch (g2k_joint_eval_f32): draw

@@ -49,7 +49,10 @@
   R > 0 also JADE_K / JFDE_K and the collision rates, one g2k_joint_eval_f32
   launch; with --kde_nll 1 also the KDE-NLL of the K draws, one g2k_kde_nll_f32
   launch; with --sample_scores 1 also their energy, variogram and diversity
-  scores, one g2k_sample_scores_f32 launch).
+  scores, one g2k_sample_scores_f32 launch; with --sample_modes M also the
+  k-means reduction of --modes_draws draws to M centres and the centres'
+  minADE_M / minFDE_M, Brier variants and miss rate, one g2k_sample_modes_f32
+  launch per head in use).
 
 The model weights are one seeded N(0, 1) draw (quirk Q15: the reference
 re-draws them every batch), padded to Nmax (8 for the node slice).
