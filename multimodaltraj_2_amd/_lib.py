@@ -188,6 +188,24 @@ def load(path: str | None = None):
     return lib
 
 
+def bind(lib, tag: str, symbols: dict):
+    """Bind ``symbols`` (a table like SYMBOLS: the entry points of a header
+    added after ABI 11) on the handle ``lib``, once per ``tag``; a library
+    without one of them is an error, there is no fallback -> ``lib``."""
+    flag = f"_g2k_{tag}_bound"
+    if not getattr(lib, flag, False):
+        for name, (res, args) in symbols.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError as e:
+                raise G2KLibraryError(f"{LIB_PATH} does not export {name}: rebuild it "
+                                      "(python __graft_entry__.py)") from e
+            fn.restype = res
+            fn.argtypes = args
+        setattr(lib, flag, True)
+    return lib
+
+
 def check(fn_name: str, rc: int):
     if rc != 0:
         msg = _lib.g2k_last_error().decode() if _lib is not None else "?"

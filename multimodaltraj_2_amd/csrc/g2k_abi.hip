@@ -1,11 +1,12 @@
 // g2k_abi.hip — the C ABI of libg2k_hip.so (include/g2k_hip.h): argument
 // validation, launch planning and the last-error plumbing.  Each entry point
 // replaces one piece of the reference's Python/TF boundary (SURVEY.md §8(b);
-// the replaced reference interface is cited in the header).
+// the replaced reference interface is cited in the header).  The sampled
+// evaluations' entry points (best-of-K, joint, KDE-NLL, scores, modes) are in
+// the files of their kernels.
 #include <stdarg.h>
 #include <stdio.h>
 
-#include "g2k_bestk_geom.h"
 #include "g2k_common.h"
 #include "g2k_mix.h"
 
@@ -527,172 +528,6 @@ int g2k_gauss_sample_f32(const g2k_dims* d, const float* pred, const float* head
   return gauss_sample_launch(d, pred, head, seed, out, (hipStream_t)stream);
 }
 
-// The argument checks of the six sampled evaluations (marginal best-of-K, joint
-// best-of-K and KDE-NLL of either head); `name` is the entry point's in the
-// message.  The marginal and KDE pairs: `out` is out, `out2` the optional
-// per_ped (16-byte aligned); the KDE pair takes K from 4 and a finite
-// log_floor.  The joint pair: `out` is sums_f, `out2` the required sums_i
-// (8-byte aligned), and radius and the workspace's alignment are checked too.
-// T and L are not looked at.  G2K_OK with S > 0: launch.
-enum SampledKind { kSampledMarginal, kSampledJoint, kSampledKde };
-
-static int validate_sampled(const char* name, SampledKind kind, const g2k_dims* d, const void* pred,
-                            const void* targets, const void* n_active, const void* head, int32_t K,
-                            float scalar, const void* out, const void* out2, const void* workspace,
-                            int64_t workspace_bytes) {
-  const bool joint = kind == kSampledJoint;
-  const int kmin = kind == kSampledKde ? 4 : 1;
-  if (!d) return set_err(G2K_EINVAL, "dims is NULL");
-  if (d->flags & G2K_STEP_PRED_PED_MAJOR)
-    return set_err(G2K_EUNSUPPORTED, "%s reads pred_path_band [S, F, 2L, Nmax]", name);
-  if (d->S < 0 || d->F < 0 || d->Nmax < 1 || d->Nmax > kMaxN)
-    return set_err(G2K_EINVAL, "S=%d F=%d Nmax=%d", d->S, d->F, d->Nmax);
-  if (K < kmin || K > 4096) return set_err(G2K_EINVAL, "K=%d (%d..4096)", K, kmin);
-  if (joint && (!(scalar >= 0.f) || scalar > 3.402823466e38f))
-    return set_err(G2K_EINVAL, "radius=%g (finite, >= 0)", (double)scalar);
-  if (kind == kSampledKde && !(scalar >= -3.402823466e38f && scalar <= 3.402823466e38f))
-    return set_err(G2K_EINVAL, "log_floor=%g (finite)", (double)scalar);
-  if (!pred || !targets || !n_active || !head || !out || (joint && !out2))
-    return set_err(G2K_EINVAL, "a required buffer pointer is NULL");
-  if (((uintptr_t)targets) & 7) return set_err(G2K_EINVAL, "targets must be 8-byte aligned");
-  if (joint && (((uintptr_t)out2) & 7)) return set_err(G2K_EINVAL, "sums_i must be 8-byte aligned");
-  if (!joint && (((uintptr_t)out2) & 15)) return set_err(G2K_EINVAL, "per_ped must be 16-byte aligned");
-  // rows of floats (the marginal and KDE pairs) or of int32 (the joint pair):
-  // a workspace that is named is held to it, an empty batch's too
-  if (workspace && (((uintptr_t)workspace) & 3))
-    return set_err(G2K_EINVAL, "workspace must be 4-byte aligned");
-  const int64_t need = joint ? joint_eval_ws_bytes(d)
-                             : kind == kSampledKde ? kde_nll_ws_bytes(d) : best_of_k_ws_bytes(d);
-  if (d->S > 0 && (!workspace || workspace_bytes < need))
-    return set_err(G2K_EINVAL, "workspace of %lld bytes needed (got %lld)%s", (long long)need,
-                   (long long)workspace_bytes, joint ? ", 4-byte aligned" : "");
-  return G2K_OK;
-}
-
-static int best_of_k(bool fullcov, const g2k_dims* d, const float* pred, const float* targets,
-                     const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
-                     const float* head, uint64_t seed, int32_t K, float* per_ped, float* best,
-                     float* out, void* workspace, int64_t workspace_bytes, void* stream) {
-  const int rc = validate_sampled(fullcov ? "fullcov_best_of_k" : "best_of_k", kSampledMarginal, d,
-                                  pred, targets, n_active, head, K, 0.f, out, per_ped, workspace,
-                                  workspace_bytes);
-  if (rc || d->S == 0) return rc;
-  return best_of_k_launch(fullcov, d, pred, targets, n_active, n_frames, ped_mask, head, seed, K,
-                          per_ped, best, out, static_cast<float*>(workspace), (hipStream_t)stream);
-}
-
-static int joint_eval(bool fullcov, const g2k_dims* d, const float* pred, const float* targets,
-                      const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
-                      const float* head, uint64_t seed, int32_t K, float radius, float* per_frame_f,
-                      int32_t* per_frame_i, float* sums_f, int64_t* sums_i, void* workspace,
-                      int64_t workspace_bytes, void* stream) {
-  const int rc = validate_sampled(fullcov ? "fullcov_joint_eval" : "joint_eval", kSampledJoint, d,
-                                  pred, targets, n_active, head, K, radius, sums_f, sums_i, workspace,
-                                  workspace_bytes);
-  if (rc || d->S == 0) return rc;
-  return joint_eval_launch(fullcov, d, pred, targets, n_active, n_frames, ped_mask, head, seed, K,
-                           radius, per_frame_f, per_frame_i, sums_f, sums_i,
-                           static_cast<int32_t*>(workspace), (hipStream_t)stream);
-}
-
-// the two heads share both evaluations' geometry, so their workspaces too
-static int64_t sampled_ws_bytes(const g2k_dims* d, bool joint) {
-  if (!d || d->S < 0 || d->F < 0) return -1;
-  return joint ? joint_eval_ws_bytes(d) : best_of_k_ws_bytes(d);
-}
-
-int64_t g2k_best_of_k_workspace_bytes(const g2k_dims* d) { return sampled_ws_bytes(d, false); }
-int64_t g2k_fullcov_best_of_k_workspace_bytes(const g2k_dims* d) { return sampled_ws_bytes(d, false); }
-int64_t g2k_joint_eval_workspace_bytes(const g2k_dims* d) { return sampled_ws_bytes(d, true); }
-int64_t g2k_fullcov_joint_eval_workspace_bytes(const g2k_dims* d) { return sampled_ws_bytes(d, true); }
-
-// the launch geometry of the per-pair sampled evaluations (bestk_geom: host
-// arithmetic, no HIP call), as the launchers work it out
-int g2k_best_of_k_geometry(const g2k_dims* d, int32_t K, int32_t* out) {
-  if (!d) return set_err(G2K_EINVAL, "dims is NULL");
-  if (d->S < 0 || d->F < 0 || d->Nmax < 1 || d->Nmax > kMaxN)
-    return set_err(G2K_EINVAL, "S=%d F=%d Nmax=%d", d->S, d->F, d->Nmax);
-  if (K < 1 || K > 4096) return set_err(G2K_EINVAL, "K=%d (1..4096)", K);
-  if (!out) return set_err(G2K_EINVAL, "out is NULL");
-  const BestkGeom g = bestk_geom(*d, K);
-  out[0] = 1 << g.ks_log2;
-  out[1] = g.FC;
-  out[2] = g.C;
-  return G2K_OK;
-}
-
-int g2k_best_of_k_f32(const g2k_dims* d, const float* pred, const float* targets,
-                      const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
-                      const float* head, uint64_t seed, int32_t K, float* per_ped, float* best,
-                      float* out, void* workspace, int64_t workspace_bytes, void* stream) {
-  return best_of_k(false, d, pred, targets, n_active, n_frames, ped_mask, head, seed, K, per_ped, best,
-                   out, workspace, workspace_bytes, stream);
-}
-
-int g2k_fullcov_best_of_k_f32(const g2k_dims* d, const float* pred, const float* targets,
-                              const int32_t* n_active, const int32_t* n_frames,
-                              const uint8_t* ped_mask, const float* chol, uint64_t seed, int32_t K,
-                              float* per_ped, float* best, float* out, void* workspace,
-                              int64_t workspace_bytes, void* stream) {
-  return best_of_k(true, d, pred, targets, n_active, n_frames, ped_mask, chol, seed, K, per_ped, best,
-                   out, workspace, workspace_bytes, stream);
-}
-
-// S == 0 or F == 0 launches nothing
-static int kde_nll(bool fullcov, const g2k_dims* d, const float* pred, const float* targets,
-                   const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
-                   const float* head, uint64_t seed, int32_t K, float log_floor, float* per_ped,
-                   float* out, void* workspace, int64_t workspace_bytes, void* stream) {
-  const int rc = validate_sampled(fullcov ? "fullcov_kde_nll" : "kde_nll", kSampledKde, d, pred,
-                                  targets, n_active, head, K, log_floor, out, per_ped, workspace,
-                                  workspace_bytes);
-  if (rc || d->S == 0 || d->F == 0) return rc;
-  return kde_nll_launch(fullcov, d, pred, targets, n_active, n_frames, ped_mask, head, seed, K,
-                        log_floor, per_ped, out, static_cast<float*>(workspace), (hipStream_t)stream);
-}
-
-int64_t g2k_kde_nll_workspace_bytes(const g2k_dims* d) {
-  if (!d || d->S < 0 || d->F < 0) return -1;
-  return kde_nll_ws_bytes(d);
-}
-int64_t g2k_fullcov_kde_nll_workspace_bytes(const g2k_dims* d) { return g2k_kde_nll_workspace_bytes(d); }
-
-int g2k_kde_nll_f32(const g2k_dims* d, const float* pred, const float* targets,
-                    const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
-                    const float* head, uint64_t seed, int32_t K, float log_floor, float* per_ped,
-                    float* out, void* workspace, int64_t workspace_bytes, void* stream) {
-  return kde_nll(false, d, pred, targets, n_active, n_frames, ped_mask, head, seed, K, log_floor,
-                 per_ped, out, workspace, workspace_bytes, stream);
-}
-
-int g2k_fullcov_kde_nll_f32(const g2k_dims* d, const float* pred, const float* targets,
-                            const int32_t* n_active, const int32_t* n_frames,
-                            const uint8_t* ped_mask, const float* chol, uint64_t seed, int32_t K,
-                            float log_floor, float* per_ped, float* out, void* workspace,
-                            int64_t workspace_bytes, void* stream) {
-  return kde_nll(true, d, pred, targets, n_active, n_frames, ped_mask, chol, seed, K, log_floor,
-                 per_ped, out, workspace, workspace_bytes, stream);
-}
-
-int g2k_joint_eval_f32(const g2k_dims* d, const float* pred, const float* targets,
-                       const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
-                       const float* head, uint64_t seed, int32_t K, float radius, float* per_frame_f,
-                       int32_t* per_frame_i, float* sums_f, int64_t* sums_i, void* workspace,
-                       int64_t workspace_bytes, void* stream) {
-  return joint_eval(false, d, pred, targets, n_active, n_frames, ped_mask, head, seed, K, radius,
-                    per_frame_f, per_frame_i, sums_f, sums_i, workspace, workspace_bytes, stream);
-}
-
-int g2k_fullcov_joint_eval_f32(const g2k_dims* d, const float* pred, const float* targets,
-                               const int32_t* n_active, const int32_t* n_frames,
-                               const uint8_t* ped_mask, const float* chol, uint64_t seed,
-                               int32_t K, float radius, float* per_frame_f, int32_t* per_frame_i,
-                               float* sums_f, int64_t* sums_i, void* workspace,
-                               int64_t workspace_bytes, void* stream) {
-  return joint_eval(true, d, pred, targets, n_active, n_frames, ped_mask, chol, seed, K, radius,
-                    per_frame_f, per_frame_i, sums_f, sums_i, workspace, workspace_bytes, stream);
-}
-
 static bool head_stats_sizes_ok(const g2k_dims* d, int32_t n_levels) {
   if (d->S < 0 || d->F < 0 || d->Nmax < 1 || d->Nmax > kMaxN) return false;
   if (n_levels < 0 || n_levels > 32) return false;
@@ -839,49 +674,6 @@ int g2k_mix_sample_f32(const g2k_dims* d, const float* pred, const float* mix, u
   if (!out) return set_err(G2K_EINVAL, "out is NULL");
   if ((int64_t)d->S * d->F * kL * d->Nmax == 0) return G2K_OK;
   return mix_sample_launch(d, pred, mix, seed, out, comp, (hipStream_t)stream);
-}
-
-int64_t g2k_mix_best_of_k_workspace_bytes(const g2k_dims* d) { return sampled_ws_bytes(d, false); }
-
-int g2k_mix_best_of_k_f32(const g2k_dims* d, const float* pred, const float* targets,
-                          const int32_t* n_active, const int32_t* n_frames,
-                          const uint8_t* ped_mask, const float* mix, uint64_t seed, int32_t K,
-                          float* per_ped, float* best, float* out, void* workspace,
-                          int64_t workspace_bytes, void* stream) {
-  const int rc = validate_sampled("mix_best_of_k", kSampledMarginal, d, pred, targets, n_active, mix,
-                                  K, 0.f, out, per_ped, workspace, workspace_bytes);
-  if (rc || d->S == 0) return rc;
-  return mix_best_of_k_launch(d, pred, targets, n_active, n_frames, ped_mask, mix, seed, K, per_ped,
-                              best, out, static_cast<float*>(workspace), (hipStream_t)stream);
-}
-
-int64_t g2k_mix_joint_eval_workspace_bytes(const g2k_dims* d) { return sampled_ws_bytes(d, true); }
-
-int g2k_mix_joint_eval_f32(const g2k_dims* d, const float* pred, const float* targets,
-                           const int32_t* n_active, const int32_t* n_frames,
-                           const uint8_t* ped_mask, const float* mix, uint64_t seed, int32_t K,
-                           float radius, float* per_frame_f, int32_t* per_frame_i, float* sums_f,
-                           int64_t* sums_i, void* workspace, int64_t workspace_bytes, void* stream) {
-  const int rc = validate_sampled("mix_joint_eval", kSampledJoint, d, pred, targets, n_active, mix, K,
-                                  radius, sums_f, sums_i, workspace, workspace_bytes);
-  if (rc || d->S == 0) return rc;
-  return mix_joint_eval_launch(d, pred, targets, n_active, n_frames, ped_mask, mix, seed, K, radius,
-                               per_frame_f, per_frame_i, sums_f, sums_i,
-                               static_cast<int32_t*>(workspace), (hipStream_t)stream);
-}
-
-int64_t g2k_mix_kde_nll_workspace_bytes(const g2k_dims* d) { return g2k_kde_nll_workspace_bytes(d); }
-
-// S == 0 or F == 0 launches nothing
-int g2k_mix_kde_nll_f32(const g2k_dims* d, const float* pred, const float* targets,
-                        const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
-                        const float* mix, uint64_t seed, int32_t K, float log_floor, float* per_ped,
-                        float* out, void* workspace, int64_t workspace_bytes, void* stream) {
-  const int rc = validate_sampled("mix_kde_nll", kSampledKde, d, pred, targets, n_active, mix, K,
-                                  log_floor, out, per_ped, workspace, workspace_bytes);
-  if (rc || d->S == 0 || d->F == 0) return rc;
-  return mix_kde_nll_launch(d, pred, targets, n_active, n_frames, ped_mask, mix, seed, K, log_floor,
-                            per_ped, out, static_cast<float*>(workspace), (hipStream_t)stream);
 }
 
 int g2k_update_f32(float* params, float* ms, const float* grad, int64_t n_params, float lr,

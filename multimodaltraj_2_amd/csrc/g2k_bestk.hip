@@ -1,11 +1,13 @@
 // g2k_bestk.hip — fused best-of-K sampling evaluation (minADE_K / minFDE_K)
 // of a probabilistic head: ONE kernel, best_of_k_kernel<Head>, instantiated
-// for the per-step bivariate-Gaussian head (g2k_best_of_k_f32) and for the
-// full-covariance trajectory head (g2k_fullcov_best_of_k_f32); the heads are
-// the policies of g2k_head_draw.h.  The build's: the reference has no
-// probabilistic head, so PARITY UNPINNED; tests/bestk_ref.py restates the
-// definition over oracle/g2k_ref.py gauss_sample, tests/fullcov_ref.py the
-// full-covariance draw.
+// for the per-step bivariate-Gaussian head (g2k_best_of_k_f32), for the
+// full-covariance trajectory head (g2k_fullcov_best_of_k_f32) and for the
+// Gaussian-mixture head (g2k_mix_best_of_k_f32, include/g2k_mix.h); the heads
+// are the policies of g2k_head_draw.h.  The C entry points, their validator
+// and g2k_best_of_k_geometry are at the end of this file.  The build's: the
+// reference has no probabilistic head, so PARITY UNPINNED; tests/bestk_ref.py
+// restates the definition over oracle/g2k_ref.py gauss_sample,
+// tests/fullcov_ref.py the full-covariance draw.
 //
 // Definition.  Inputs as g2k_nll_f32: pred [S, F, 2L, Nmax] (band layout),
 // targets [S, F, Nmax, L, 2] ([S, 1, Nmax, L, 2] with G2K_STEP_TARGETS_SHARED),
@@ -47,8 +49,10 @@
 // g2k_bestk_rows_kernel adds a scene's C rows in chunk order (no atomics);
 // C == 1 writes out directly.
 #include "g2k_bestk_geom.h"
+#include "g2k_checks.h"
 #include "g2k_common.h"
 #include "g2k_head_draw.h"
+#include "g2k_mix.h"
 
 namespace g2k {
 namespace {
@@ -215,29 +219,96 @@ int best_of_k_launch_as(const g2k_dims* d, const float* pred, const float* targe
   return check_launch("g2k_bestk_rows_kernel");
 }
 
-}  // namespace
-
 // one row [8] per (scene, chunk); FC >= 1 frame per chunk, so at most F chunks
 int64_t best_of_k_ws_bytes(const g2k_dims* d) {
+  if (!d || d->S < 0 || d->F < 0) return -1;
   return (int64_t)d->S * (d->F > 1 ? d->F : 1) * 8 * 4;
 }
 
-int best_of_k_launch(bool fullcov, const g2k_dims* d, const float* pred, const float* targets,
-                     const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
-                     const float* head, uint64_t seed, int K, float* per_ped, float* best, float* out,
-                     float* rows, hipStream_t st) {
-  return (fullcov ? best_of_k_launch_as<FullCovHead> : best_of_k_launch_as<PerStepHead>)(
-      d, pred, targets, n_active, n_frames, ped_mask, head, seed, K, per_ped, best, out, rows, st);
+// the argument checks, before any HIP call; `name` is the entry point's in the
+// message; G2K_OK with S > 0: launch
+int best_of_k_validate(const char* name, const g2k_dims* d, const void* pred, const void* targets,
+                       const void* n_active, const void* head, int32_t K, const void* per_ped,
+                       const void* out, const void* workspace, int64_t workspace_bytes) {
+  if (const int rc = check_dims(d)) return rc;
+  if (d->flags & G2K_STEP_PRED_PED_MAJOR)
+    return set_err(G2K_EUNSUPPORTED, "%s reads pred_path_band [S, F, 2L, Nmax]", name);
+  if (const int rc = check_pair_sizes(d)) return rc;
+  if (K < 1 || K > 4096) return set_err(G2K_EINVAL, "K=%d (1..4096)", K);
+  if (const int rc = check_required({pred, targets, n_active, head, out})) return rc;
+  if (const int rc = check_targets(targets)) return rc;
+  if (const int rc = check_per_ped(per_ped)) return rc;
+  return check_workspace(d, workspace, workspace_bytes, best_of_k_ws_bytes(d), 4);   // rows of floats
 }
 
-// the Gaussian-mixture head (g2k_mix_best_of_k_f32): the same kernel with the
-// MixHead policy, mix [8][608]; geometry and workspace as the other two
-int mix_best_of_k_launch(const g2k_dims* d, const float* pred, const float* targets,
-                         const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
-                         const float* mix, uint64_t seed, int K, float* per_ped, float* best,
-                         float* out, float* rows, hipStream_t st) {
-  return best_of_k_launch_as<MixHead>(d, pred, targets, n_active, n_frames, ped_mask, mix, seed, K,
-                                      per_ped, best, out, rows, st);
+template <class Head>
+int best_of_k(const char* name, const g2k_dims* d, const float* pred, const float* targets,
+              const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+              const float* head, uint64_t seed, int32_t K, float* per_ped, float* best, float* out,
+              void* workspace, int64_t workspace_bytes, void* stream) {
+  const int rc = best_of_k_validate(name, d, pred, targets, n_active, head, K, per_ped, out, workspace,
+                                    workspace_bytes);
+  if (rc || d->S == 0) return rc;
+  return best_of_k_launch_as<Head>(d, pred, targets, n_active, n_frames, ped_mask, head, seed, K,
+                                   per_ped, best, out, static_cast<float*>(workspace),
+                                   (hipStream_t)stream);
 }
 
+}  // namespace
 }  // namespace g2k
+
+using namespace g2k;
+
+extern "C" {
+
+// the three heads share the geometry, so the workspace too
+int64_t g2k_best_of_k_workspace_bytes(const g2k_dims* d) { return best_of_k_ws_bytes(d); }
+int64_t g2k_fullcov_best_of_k_workspace_bytes(const g2k_dims* d) { return best_of_k_ws_bytes(d); }
+int64_t g2k_mix_best_of_k_workspace_bytes(const g2k_dims* d) { return best_of_k_ws_bytes(d); }
+
+// the launch geometry of the per-pair sampled evaluations (bestk_geom: host
+// arithmetic, no HIP call), as the launchers work it out
+int g2k_best_of_k_geometry(const g2k_dims* d, int32_t K, int32_t* out) {
+  if (const int rc = check_dims(d)) return rc;
+  if (const int rc = check_pair_sizes(d)) return rc;
+  if (K < 1 || K > 4096) return set_err(G2K_EINVAL, "K=%d (1..4096)", K);
+  if (!out) return set_err(G2K_EINVAL, "out is NULL");
+  const BestkGeom g = bestk_geom(*d, K);
+  out[0] = 1 << g.ks_log2;
+  out[1] = g.FC;
+  out[2] = g.C;
+  return G2K_OK;
+}
+
+// The full-covariance head's comes first in each of the three families of
+// this kind (here, g2k_joint.hip, g2k_kde.hip): a kernel is emitted where its
+// instantiation is first named, and that is the order the code objects have
+// always had.
+int g2k_fullcov_best_of_k_f32(const g2k_dims* d, const float* pred, const float* targets,
+                              const int32_t* n_active, const int32_t* n_frames,
+                              const uint8_t* ped_mask, const float* chol, uint64_t seed, int32_t K,
+                              float* per_ped, float* best, float* out, void* workspace,
+                              int64_t workspace_bytes, void* stream) {
+  return best_of_k<FullCovHead>("fullcov_best_of_k", d, pred, targets, n_active, n_frames, ped_mask,
+                                chol, seed, K, per_ped, best, out, workspace, workspace_bytes, stream);
+}
+
+int g2k_best_of_k_f32(const g2k_dims* d, const float* pred, const float* targets,
+                      const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                      const float* head, uint64_t seed, int32_t K, float* per_ped, float* best,
+                      float* out, void* workspace, int64_t workspace_bytes, void* stream) {
+  return best_of_k<PerStepHead>("best_of_k", d, pred, targets, n_active, n_frames, ped_mask, head, seed,
+                                K, per_ped, best, out, workspace, workspace_bytes, stream);
+}
+
+// mix [8][608] (include/g2k_mix.h)
+int g2k_mix_best_of_k_f32(const g2k_dims* d, const float* pred, const float* targets,
+                          const int32_t* n_active, const int32_t* n_frames,
+                          const uint8_t* ped_mask, const float* mix, uint64_t seed, int32_t K,
+                          float* per_ped, float* best, float* out, void* workspace,
+                          int64_t workspace_bytes, void* stream) {
+  return best_of_k<MixHead>("mix_best_of_k", d, pred, targets, n_active, n_frames, ped_mask, mix, seed,
+                            K, per_ped, best, out, workspace, workspace_bytes, stream);
+}
+
+}  // extern "C"

@@ -1,7 +1,9 @@
 // g2k_common.h — shared constants, wave-level helpers and host launcher
 // declarations of the gfx950 (CDNA4) implementation of the g2k_lstm_mcr
 // per-frame path.  Included by every .hip
-// translation unit of libg2k_hip.so; the C ABI is in g2k_abi.hip.
+// translation unit of libg2k_hip.so; the C ABI is in g2k_abi.hip, but for the
+// sampled evaluations' entry points, which are in the files of their kernels
+// (g2k_bestk.hip, g2k_joint.hip, g2k_kde.hip, g2k_scores.hip, g2k_modes.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -525,28 +527,6 @@ int nll_launch(const g2k_dims* d, const float* pred, const float* targets, const
 int gauss_sample_launch(const g2k_dims* d, const float* pred, const float* head, uint64_t seed,
                         float* out, hipStream_t st);
 
-// g2k_bestk.hip, g2k_joint.hip: the fused evaluations of the per-step head
-// (head [3, 12]) or, with `fullcov`, of the full-covariance head (head = chol
-// [24, 24])
-int64_t best_of_k_ws_bytes(const g2k_dims* d);
-int best_of_k_launch(bool fullcov, const g2k_dims* d, const float* pred, const float* targets,
-                     const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
-                     const float* head, uint64_t seed, int K, float* per_ped, float* best, float* out,
-                     float* rows, hipStream_t st);
-int64_t joint_eval_ws_bytes(const g2k_dims* d);
-int joint_eval_launch(bool fullcov, const g2k_dims* d, const float* pred, const float* targets,
-                      const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
-                      const float* head, uint64_t seed, int K, float radius, float* per_frame_f,
-                      int32_t* per_frame_i, float* sums_f, int64_t* sums_i, int32_t* rows,
-                      hipStream_t st);
-
-// g2k_kde.hip: the fused KDE-NLL of either head's samples (head as above)
-int64_t kde_nll_ws_bytes(const g2k_dims* d);
-int kde_nll_launch(bool fullcov, const g2k_dims* d, const float* pred, const float* targets,
-                   const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
-                   const float* head, uint64_t seed, int K, float log_floor, float* per_ped, float* out,
-                   float* rows, hipStream_t st);
-
 // g2k_calib.hip
 int64_t head_stats_ws_bytes(const g2k_dims* d, int n_levels);
 int head_stats_launch(const g2k_dims* d, const float* pred, const float* targets,
@@ -563,9 +543,7 @@ int fullcov_stats_launch(const g2k_dims* d, const float* pred, const float* targ
 int fullcov_sample_launch(const g2k_dims* d, const float* pred, const float* chol, uint64_t seed,
                           float* out, hipStream_t st);
 
-// g2k_mix.hip (the Gaussian-mixture head, include/g2k_mix.h) and its fused
-// evaluations (g2k_bestk.hip, g2k_joint.hip, g2k_kde.hip with the MixHead
-// policy; geometry and workspaces are the other heads')
+// g2k_mix.hip (the Gaussian-mixture head, include/g2k_mix.h)
 int64_t mix_em_ws_bytes(const g2k_dims* d);
 int mix_em_launch(const g2k_dims* d, const float* pred, const float* targets,
                   const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
@@ -573,19 +551,6 @@ int mix_em_launch(const g2k_dims* d, const float* pred, const float* targets,
                   void* workspace, hipStream_t st);
 int mix_sample_launch(const g2k_dims* d, const float* pred, const float* mix, uint64_t seed,
                       float* out, int32_t* comp, hipStream_t st);
-int mix_best_of_k_launch(const g2k_dims* d, const float* pred, const float* targets,
-                         const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
-                         const float* mix, uint64_t seed, int K, float* per_ped, float* best,
-                         float* out, float* rows, hipStream_t st);
-int mix_joint_eval_launch(const g2k_dims* d, const float* pred, const float* targets,
-                          const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
-                          const float* mix, uint64_t seed, int K, float radius, float* per_frame_f,
-                          int32_t* per_frame_i, float* sums_f, int64_t* sums_i, int32_t* rows,
-                          hipStream_t st);
-int mix_kde_nll_launch(const g2k_dims* d, const float* pred, const float* targets,
-                       const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
-                       const float* mix, uint64_t seed, int K, float log_floor, float* per_ped,
-                       float* out, float* rows, hipStream_t st);
 
 // g2k_ops.hip
 int recur_launch(const float* A, float* h, int S, int frames, int D, int H, hipStream_t st);

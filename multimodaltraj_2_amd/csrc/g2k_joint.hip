@@ -5,7 +5,8 @@
 // the per-step bivariate-Gaussian head (g2k_joint_eval_f32), for the
 // full-covariance trajectory head (g2k_fullcov_joint_eval_f32) and for the
 // Gaussian-mixture head (g2k_mix_joint_eval_f32, include/g2k_mix.h); the heads
-// are the policies of g2k_head_draw.h.  The build's: the reference has no
+// are the policies of g2k_head_draw.h.  The C entry points and their validator
+// are at the end of this file.  The build's: the reference has no
 // probabilistic head, so PARITY UNPINNED; tests/joint_ref.py restates the
 // definition over oracle/g2k_ref.py gauss_sample and tests/bestk_ref.py,
 // tests/fullcov_joint_ref.py over tests/fullcov_ref.py, tests/mix_eval_ref.py
@@ -68,8 +69,10 @@
 // then the butterfly).  No atomics: results are bit-identical from run to run
 // and, JADE_k being computed the same way in whichever unit draws k, do not
 // depend on KD.
+#include "g2k_checks.h"
 #include "g2k_common.h"
 #include "g2k_head_draw.h"
+#include "g2k_mix.h"
 
 namespace g2k {
 namespace {
@@ -501,37 +504,93 @@ int joint_eval_launch_as(const g2k_dims* d, const float* pred, const float* targ
   return check_launch("g2k_joint_rows_kernel");
 }
 
-}  // namespace
-
 // one row [10] per unit; at most joint_kd_max units per scene-frame
 int64_t joint_eval_ws_bytes(const g2k_dims* d) {
+  if (!d || d->S < 0 || d->F < 0) return -1;
   return (int64_t)d->S * (d->F > 1 ? d->F : 1) * joint_kd_max(*d) * kJtRow * 4;
 }
 
-int joint_eval_launch(bool fullcov, const g2k_dims* d, const float* pred, const float* targets,
-                      const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
-                      const float* head, uint64_t seed, int K, float radius, float* per_frame_f,
-                      int32_t* per_frame_i, float* sums_f, int64_t* sums_i, int32_t* rows,
-                      hipStream_t st) {
-  return (fullcov ? joint_eval_launch_as<FullCovHead> : joint_eval_launch_as<PerStepHead>)(
-      d, pred, targets, n_active, n_frames, ped_mask, head, seed, K, radius, per_frame_f, per_frame_i,
-      sums_f, sums_i, rows, st);
+// the argument checks, before any HIP call; `name` is the entry point's in the
+// message; G2K_OK with S > 0: launch
+int joint_eval_validate(const char* name, const g2k_dims* d, const void* pred, const void* targets,
+                        const void* n_active, const void* head, int32_t K, float radius,
+                        const void* sums_f, const void* sums_i, const void* workspace,
+                        int64_t workspace_bytes) {
+  if (const int rc = check_dims(d)) return rc;
+  if (d->flags & G2K_STEP_PRED_PED_MAJOR)
+    return set_err(G2K_EUNSUPPORTED, "%s reads pred_path_band [S, F, 2L, Nmax]", name);
+  if (const int rc = check_pair_sizes(d)) return rc;
+  if (K < 1 || K > 4096) return set_err(G2K_EINVAL, "K=%d (1..4096)", K);
+  if (!(radius >= 0.f) || radius > 3.402823466e38f)
+    return set_err(G2K_EINVAL, "radius=%g (finite, >= 0)", (double)radius);
+  if (const int rc = check_required({pred, targets, n_active, head, sums_f, sums_i})) return rc;
+  if (const int rc = check_targets(targets)) return rc;
+  if (((uintptr_t)sums_i) & 7) return set_err(G2K_EINVAL, "sums_i must be 8-byte aligned");
+  // rows of int32
+  return check_workspace(d, workspace, workspace_bytes, joint_eval_ws_bytes(d), 4, ", 4-byte aligned");
 }
 
-// the Gaussian-mixture head (g2k_mix_joint_eval_f32): the same kernels with
-// the MixHead policy, mix [8][608]; geometry and workspace as the other two.
-// Every member selects its own component, so one joint sample mixes components
-// across the members of a scene-frame.  joint_kernel<MixHead> holds 69.7 KB of
-// static LDS (the double-buffered sample, 48 KB, beside the eight staged
-// factors): above 64 KB, inside gfx950's 160 KB per workgroup, two workgroups
-// per CU.
-int mix_joint_eval_launch(const g2k_dims* d, const float* pred, const float* targets,
-                          const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
-                          const float* mix, uint64_t seed, int K, float radius, float* per_frame_f,
-                          int32_t* per_frame_i, float* sums_f, int64_t* sums_i, int32_t* rows,
-                          hipStream_t st) {
-  return joint_eval_launch_as<MixHead>(d, pred, targets, n_active, n_frames, ped_mask, mix, seed, K,
-                                       radius, per_frame_f, per_frame_i, sums_f, sums_i, rows, st);
+template <class Head>
+int joint_eval(const char* name, const g2k_dims* d, const float* pred, const float* targets,
+               const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+               const float* head, uint64_t seed, int32_t K, float radius, float* per_frame_f,
+               int32_t* per_frame_i, float* sums_f, int64_t* sums_i, void* workspace,
+               int64_t workspace_bytes, void* stream) {
+  const int rc = joint_eval_validate(name, d, pred, targets, n_active, head, K, radius, sums_f, sums_i,
+                                     workspace, workspace_bytes);
+  if (rc || d->S == 0) return rc;
+  return joint_eval_launch_as<Head>(d, pred, targets, n_active, n_frames, ped_mask, head, seed, K,
+                                    radius, per_frame_f, per_frame_i, sums_f, sums_i,
+                                    static_cast<int32_t*>(workspace), (hipStream_t)stream);
 }
 
+}  // namespace
 }  // namespace g2k
+
+using namespace g2k;
+
+extern "C" {
+
+// the three heads share the geometry, so the workspace too
+int64_t g2k_joint_eval_workspace_bytes(const g2k_dims* d) { return joint_eval_ws_bytes(d); }
+int64_t g2k_fullcov_joint_eval_workspace_bytes(const g2k_dims* d) { return joint_eval_ws_bytes(d); }
+int64_t g2k_mix_joint_eval_workspace_bytes(const g2k_dims* d) { return joint_eval_ws_bytes(d); }
+
+// the full-covariance head's first: see g2k_bestk.hip
+int g2k_fullcov_joint_eval_f32(const g2k_dims* d, const float* pred, const float* targets,
+                               const int32_t* n_active, const int32_t* n_frames,
+                               const uint8_t* ped_mask, const float* chol, uint64_t seed,
+                               int32_t K, float radius, float* per_frame_f, int32_t* per_frame_i,
+                               float* sums_f, int64_t* sums_i, void* workspace,
+                               int64_t workspace_bytes, void* stream) {
+  return joint_eval<FullCovHead>("fullcov_joint_eval", d, pred, targets, n_active, n_frames, ped_mask,
+                                 chol, seed, K, radius, per_frame_f, per_frame_i, sums_f, sums_i,
+                                 workspace, workspace_bytes, stream);
+}
+
+int g2k_joint_eval_f32(const g2k_dims* d, const float* pred, const float* targets,
+                       const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                       const float* head, uint64_t seed, int32_t K, float radius, float* per_frame_f,
+                       int32_t* per_frame_i, float* sums_f, int64_t* sums_i, void* workspace,
+                       int64_t workspace_bytes, void* stream) {
+  return joint_eval<PerStepHead>("joint_eval", d, pred, targets, n_active, n_frames, ped_mask, head,
+                                 seed, K, radius, per_frame_f, per_frame_i, sums_f, sums_i, workspace,
+                                 workspace_bytes, stream);
+}
+
+// mix [8][608] (include/g2k_mix.h).  Every member selects its own component,
+// so one joint sample mixes components across the members of a scene-frame.
+// joint_kernel<MixHead> holds 69.7 KB of static LDS (the double-buffered
+// sample, 48 KB, beside the eight staged factors): above 64 KB, inside
+// gfx950's 160 KB per workgroup, two workgroups per CU.
+int g2k_mix_joint_eval_f32(const g2k_dims* d, const float* pred, const float* targets,
+                           const int32_t* n_active, const int32_t* n_frames,
+                           const uint8_t* ped_mask, const float* mix, uint64_t seed, int32_t K,
+                           float radius, float* per_frame_f, int32_t* per_frame_i, float* sums_f,
+                           int64_t* sums_i, void* workspace, int64_t workspace_bytes, void* stream) {
+  return joint_eval<MixHead>("mix_joint_eval", d, pred, targets, n_active, n_frames, ped_mask, mix,
+                             seed, K, radius, per_frame_f, per_frame_i, sums_f, sums_i, workspace,
+                             workspace_bytes, stream);
+}
+
+}  // extern "C"

@@ -3,9 +3,10 @@
 // for the per-step bivariate-Gaussian head (g2k_kde_nll_f32), for the
 // full-covariance trajectory head (g2k_fullcov_kde_nll_f32) and for the
 // Gaussian-mixture head (g2k_mix_kde_nll_f32, include/g2k_mix.h); the heads are
-// the policies of g2k_head_draw.h.  The build's: the reference has no
-// probabilistic head, so PARITY UNPINNED; pinned against
-// scipy.stats.gaussian_kde through tests/kde_ref.py.
+// the policies of g2k_head_draw.h.  The C entry points and their validator are
+// at the end of this file.  The build's: the reference has no probabilistic
+// head, so PARITY UNPINNED; pinned against scipy.stats.gaussian_kde through
+// tests/kde_ref.py.
 //
 // Definition.  Inputs and pairs as g2k_best_of_k_f32 (g2k_bestk.hip), K in
 // [4, 4096], log_floor finite.  Draw k = what the head's sampler writes for
@@ -55,8 +56,10 @@
 // g2k_kde_rows_kernel adds a scene's C rows in chunk order; C == 1 writes out
 // directly.
 #include "g2k_bestk_geom.h"
+#include "g2k_checks.h"
 #include "g2k_common.h"
 #include "g2k_head_draw.h"
+#include "g2k_mix.h"
 
 namespace g2k {
 namespace {
@@ -303,30 +306,83 @@ int kde_nll_launch_as(const g2k_dims* d, const float* pred, const float* targets
   return check_launch("g2k_kde_rows_kernel");
 }
 
-}  // namespace
-
 // one row [8] per (scene, chunk); FC >= 1 frame per chunk, so at most F chunks
 int64_t kde_nll_ws_bytes(const g2k_dims* d) {
+  if (!d || d->S < 0 || d->F < 0) return -1;
   return (int64_t)d->S * (d->F > 1 ? d->F : 1) * 8 * 4;
 }
 
-int kde_nll_launch(bool fullcov, const g2k_dims* d, const float* pred, const float* targets,
-                   const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
-                   const float* head, uint64_t seed, int K, float log_floor, float* per_ped, float* out,
-                   float* rows, hipStream_t st) {
-  return (fullcov ? kde_nll_launch_as<FullCovHead> : kde_nll_launch_as<PerStepHead>)(
-      d, pred, targets, n_active, n_frames, ped_mask, head, seed, K, log_floor, per_ped, out, rows, st);
+// the argument checks, before any HIP call; `name` is the entry point's in the
+// message; G2K_OK with S > 0 and F > 0: launch
+int kde_nll_validate(const char* name, const g2k_dims* d, const void* pred, const void* targets,
+                     const void* n_active, const void* head, int32_t K, float log_floor,
+                     const void* per_ped, const void* out, const void* workspace,
+                     int64_t workspace_bytes) {
+  if (const int rc = check_dims(d)) return rc;
+  if (d->flags & G2K_STEP_PRED_PED_MAJOR)
+    return set_err(G2K_EUNSUPPORTED, "%s reads pred_path_band [S, F, 2L, Nmax]", name);
+  if (const int rc = check_pair_sizes(d)) return rc;
+  if (K < 4 || K > 4096) return set_err(G2K_EINVAL, "K=%d (4..4096)", K);
+  if (!(log_floor >= -3.402823466e38f && log_floor <= 3.402823466e38f))
+    return set_err(G2K_EINVAL, "log_floor=%g (finite)", (double)log_floor);
+  if (const int rc = check_required({pred, targets, n_active, head, out})) return rc;
+  if (const int rc = check_targets(targets)) return rc;
+  if (const int rc = check_per_ped(per_ped)) return rc;
+  return check_workspace(d, workspace, workspace_bytes, kde_nll_ws_bytes(d), 4);   // rows of floats
 }
 
-// the Gaussian-mixture head (g2k_mix_kde_nll_f32): the same kernel with the
-// MixHead policy, mix [8][608], and the running-mean moments; geometry and
-// workspace as the other two
-int mix_kde_nll_launch(const g2k_dims* d, const float* pred, const float* targets,
-                       const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
-                       const float* mix, uint64_t seed, int K, float log_floor, float* per_ped,
-                       float* out, float* rows, hipStream_t st) {
-  return kde_nll_launch_as<MixHead>(d, pred, targets, n_active, n_frames, ped_mask, mix, seed, K,
-                                    log_floor, per_ped, out, rows, st);
+// S == 0 or F == 0 launches nothing
+template <class Head>
+int kde_nll(const char* name, const g2k_dims* d, const float* pred, const float* targets,
+            const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+            const float* head, uint64_t seed, int32_t K, float log_floor, float* per_ped, float* out,
+            void* workspace, int64_t workspace_bytes, void* stream) {
+  const int rc = kde_nll_validate(name, d, pred, targets, n_active, head, K, log_floor, per_ped, out,
+                                  workspace, workspace_bytes);
+  if (rc || d->S == 0 || d->F == 0) return rc;
+  return kde_nll_launch_as<Head>(d, pred, targets, n_active, n_frames, ped_mask, head, seed, K,
+                                 log_floor, per_ped, out, static_cast<float*>(workspace),
+                                 (hipStream_t)stream);
 }
 
+}  // namespace
 }  // namespace g2k
+
+using namespace g2k;
+
+extern "C" {
+
+// the three heads share the geometry, so the workspace too
+int64_t g2k_kde_nll_workspace_bytes(const g2k_dims* d) { return kde_nll_ws_bytes(d); }
+int64_t g2k_fullcov_kde_nll_workspace_bytes(const g2k_dims* d) { return kde_nll_ws_bytes(d); }
+int64_t g2k_mix_kde_nll_workspace_bytes(const g2k_dims* d) { return kde_nll_ws_bytes(d); }
+
+// the full-covariance head's first: see g2k_bestk.hip
+int g2k_fullcov_kde_nll_f32(const g2k_dims* d, const float* pred, const float* targets,
+                            const int32_t* n_active, const int32_t* n_frames,
+                            const uint8_t* ped_mask, const float* chol, uint64_t seed, int32_t K,
+                            float log_floor, float* per_ped, float* out, void* workspace,
+                            int64_t workspace_bytes, void* stream) {
+  return kde_nll<FullCovHead>("fullcov_kde_nll", d, pred, targets, n_active, n_frames, ped_mask, chol,
+                              seed, K, log_floor, per_ped, out, workspace, workspace_bytes, stream);
+}
+
+int g2k_kde_nll_f32(const g2k_dims* d, const float* pred, const float* targets,
+                    const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                    const float* head, uint64_t seed, int32_t K, float log_floor, float* per_ped,
+                    float* out, void* workspace, int64_t workspace_bytes, void* stream) {
+  return kde_nll<PerStepHead>("kde_nll", d, pred, targets, n_active, n_frames, ped_mask, head, seed, K,
+                              log_floor, per_ped, out, workspace, workspace_bytes, stream);
+}
+
+// mix [8][608] (include/g2k_mix.h); the kernel keeps running-mean moments
+// for this head (Head::kKdeRunningMean)
+int g2k_mix_kde_nll_f32(const g2k_dims* d, const float* pred, const float* targets,
+                        const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
+                        const float* mix, uint64_t seed, int32_t K, float log_floor, float* per_ped,
+                        float* out, void* workspace, int64_t workspace_bytes, void* stream) {
+  return kde_nll<MixHead>("mix_kde_nll", d, pred, targets, n_active, n_frames, ped_mask, mix, seed, K,
+                          log_floor, per_ped, out, workspace, workspace_bytes, stream);
+}
+
+}  // extern "C"

@@ -41,6 +41,7 @@
 // chunk order and rounds once; C == 1 rounds and writes out directly.
 #include <math.h>
 
+#include "g2k_checks.h"
 #include "g2k_common.h"
 #include "g2k_head_draw.h"
 #include "g2k_modes.h"
@@ -374,10 +375,6 @@ int sample_modes_launch(const g2k_dims* d, const float* pred, const float* targe
   return check_launch("g2k_modes_rows_kernel");
 }
 
-bool modes_dims_ok(const g2k_dims* d) {
-  return d->S >= 0 && d->F >= 0 && d->Nmax >= 1 && d->Nmax <= kMaxN;
-}
-
 // one row [8] of doubles per (scene, chunk); FC >= 1 frame per chunk, so at most F chunks
 int64_t modes_ws_bytes(const g2k_dims* d) {
   return (int64_t)d->S * (d->F > 1 ? d->F : 1) * 8 * 8;
@@ -395,26 +392,19 @@ int modes_validate(const char* name, const g2k_dims* d, const void* pred, const 
                    const void* n_active, const void* head, int32_t K, int32_t M, int32_t iters,
                    float miss_radius, const void* per_ped, const void* out, const void* workspace,
                    int64_t workspace_bytes) {
-  if (!d) return set_err(G2K_EINVAL, "dims is NULL");
+  if (const int rc = check_dims(d)) return rc;
   if (d->flags & ~G2K_STEP_TARGETS_SHARED)
     return set_err(G2K_EUNSUPPORTED, "%s: flags %d (0 or G2K_STEP_TARGETS_SHARED)", name, d->flags);
-  if (!modes_dims_ok(d)) return set_err(G2K_EINVAL, "S=%d F=%d Nmax=%d", d->S, d->F, d->Nmax);
+  if (const int rc = check_pair_sizes(d)) return rc;
   if (const int rc = modes_params_ok(K, M)) return rc;
   if (iters < 0 || iters > G2K_MODES_ITERS_MAX)
     return set_err(G2K_EINVAL, "iters=%d (0..%d)", iters, G2K_MODES_ITERS_MAX);
   if (!(miss_radius >= 0.f) || !isfinite(miss_radius))
     return set_err(G2K_EINVAL, "miss_radius=%g (finite, >= 0)", (double)miss_radius);
-  if (!pred || !targets || !n_active || !head || !out)
-    return set_err(G2K_EINVAL, "a required buffer pointer is NULL");
-  if (((uintptr_t)targets) & 7) return set_err(G2K_EINVAL, "targets must be 8-byte aligned");
-  if (((uintptr_t)per_ped) & 15) return set_err(G2K_EINVAL, "per_ped must be 16-byte aligned");
-  if (workspace && (((uintptr_t)workspace) & 7))
-    return set_err(G2K_EINVAL, "workspace must be 8-byte aligned");
-  const int64_t need = modes_ws_bytes(d);
-  if (d->S > 0 && (!workspace || workspace_bytes < need))
-    return set_err(G2K_EINVAL, "workspace of %lld bytes needed (got %lld)", (long long)need,
-                   (long long)workspace_bytes);
-  return G2K_OK;
+  if (const int rc = check_required({pred, targets, n_active, head, out})) return rc;
+  if (const int rc = check_targets(targets)) return rc;
+  if (const int rc = check_per_ped(per_ped)) return rc;
+  return check_workspace(d, workspace, workspace_bytes, modes_ws_bytes(d), 8);   // rows of doubles
 }
 
 template <class Head>
@@ -439,15 +429,15 @@ using namespace g2k;
 extern "C" {
 
 int64_t g2k_sample_modes_workspace_bytes(const g2k_dims* d) {
-  if (!d || !modes_dims_ok(d)) return -1;
+  if (!d || !pair_sizes_ok(d)) return -1;
   return modes_ws_bytes(d);
 }
 
 // the launch geometry (modes_geom: host arithmetic, no HIP call), as the
 // launcher works it out
 int g2k_sample_modes_geometry(const g2k_dims* d, int32_t K, int32_t M, int32_t* out) {
-  if (!d) return set_err(G2K_EINVAL, "dims is NULL");
-  if (!modes_dims_ok(d)) return set_err(G2K_EINVAL, "S=%d F=%d Nmax=%d", d->S, d->F, d->Nmax);
+  if (const int rc = check_dims(d)) return rc;
+  if (const int rc = check_pair_sizes(d)) return rc;
   if (const int rc = modes_params_ok(K, M)) return rc;
   if (!out) return set_err(G2K_EINVAL, "out is NULL");
   const ModesGeom g = modes_geom(*d, K, M);

@@ -55,6 +55,7 @@
 // Scene sums: per-workgroup rows [S * C][8] in the caller's workspace, then
 // g2k_scores_rows_kernel adds a scene's C rows in chunk order; C == 1 writes
 // out directly.
+#include "g2k_checks.h"
 #include "g2k_common.h"
 #include "g2k_head_draw.h"
 #include "g2k_scores.h"
@@ -303,10 +304,6 @@ int sample_scores_launch(const g2k_dims* d, const float* pred, const float* targ
   return check_launch("g2k_scores_rows_kernel");
 }
 
-bool scores_dims_ok(const g2k_dims* d) {
-  return d->S >= 0 && d->F >= 0 && d->Nmax >= 1 && d->Nmax <= kMaxN;
-}
-
 // one row [8] per (scene, chunk); FC >= 1 frame per chunk, so at most F chunks
 int64_t scores_ws_bytes(const g2k_dims* d) {
   return (int64_t)d->S * (d->F > 1 ? d->F : 1) * 8 * 4;
@@ -316,23 +313,16 @@ int64_t scores_ws_bytes(const g2k_dims* d) {
 int scores_validate(const char* name, const g2k_dims* d, const void* pred, const void* targets,
                     const void* n_active, const void* head, int32_t K, const void* per_ped,
                     const void* out, const void* workspace, int64_t workspace_bytes) {
-  if (!d) return set_err(G2K_EINVAL, "dims is NULL");
+  if (const int rc = check_dims(d)) return rc;
   if (d->flags & ~G2K_STEP_TARGETS_SHARED)
     return set_err(G2K_EUNSUPPORTED, "%s: flags %d (0 or G2K_STEP_TARGETS_SHARED)", name, d->flags);
-  if (!scores_dims_ok(d)) return set_err(G2K_EINVAL, "S=%d F=%d Nmax=%d", d->S, d->F, d->Nmax);
+  if (const int rc = check_pair_sizes(d)) return rc;
   if (K < G2K_SCORES_KMIN || K > G2K_SCORES_KMAX)
     return set_err(G2K_EINVAL, "K=%d (%d..%d)", K, G2K_SCORES_KMIN, G2K_SCORES_KMAX);
-  if (!pred || !targets || !n_active || !head || !out)
-    return set_err(G2K_EINVAL, "a required buffer pointer is NULL");
-  if (((uintptr_t)targets) & 7) return set_err(G2K_EINVAL, "targets must be 8-byte aligned");
-  if (((uintptr_t)per_ped) & 15) return set_err(G2K_EINVAL, "per_ped must be 16-byte aligned");
-  if (workspace && (((uintptr_t)workspace) & 3))
-    return set_err(G2K_EINVAL, "workspace must be 4-byte aligned");
-  const int64_t need = scores_ws_bytes(d);
-  if (d->S > 0 && (!workspace || workspace_bytes < need))
-    return set_err(G2K_EINVAL, "workspace of %lld bytes needed (got %lld)", (long long)need,
-                   (long long)workspace_bytes);
-  return G2K_OK;
+  if (const int rc = check_required({pred, targets, n_active, head, out})) return rc;
+  if (const int rc = check_targets(targets)) return rc;
+  if (const int rc = check_per_ped(per_ped)) return rc;
+  return check_workspace(d, workspace, workspace_bytes, scores_ws_bytes(d), 4);   // rows of floats
 }
 
 template <class Head>
@@ -355,15 +345,15 @@ using namespace g2k;
 extern "C" {
 
 int64_t g2k_sample_scores_workspace_bytes(const g2k_dims* d) {
-  if (!d || !scores_dims_ok(d)) return -1;
+  if (!d || !pair_sizes_ok(d)) return -1;
   return scores_ws_bytes(d);
 }
 
 // the launch geometry (scores_geom: host arithmetic, no HIP call), as the
 // launcher works it out
 int g2k_sample_scores_geometry(const g2k_dims* d, int32_t K, int32_t* out) {
-  if (!d) return set_err(G2K_EINVAL, "dims is NULL");
-  if (!scores_dims_ok(d)) return set_err(G2K_EINVAL, "S=%d F=%d Nmax=%d", d->S, d->F, d->Nmax);
+  if (const int rc = check_dims(d)) return rc;
+  if (const int rc = check_pair_sizes(d)) return rc;
   if (K < G2K_SCORES_KMIN || K > G2K_SCORES_KMAX)
     return set_err(G2K_EINVAL, "K=%d (%d..%d)", K, G2K_SCORES_KMIN, G2K_SCORES_KMAX);
   if (!out) return set_err(G2K_EINVAL, "out is NULL");

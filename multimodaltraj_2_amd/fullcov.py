@@ -25,9 +25,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .frame_step import OBS_LEN, PRED_LEN, _check_dev, _ptr, _stream
-from .nll import (DEFAULT_LEVELS, MAX_LEVELS, _best_of_k, _check_pairs_inputs, _joint_eval,
-                  _kde_nll)
+from .frame_step import PRED_LEN, _check_dev, _ptr, _stream
+from .nll import DEFAULT_LEVELS, MAX_LEVELS, SampledEvals, _check_pairs_inputs
 
 DIM = 2 * PRED_LEN
 
@@ -163,7 +162,17 @@ class FullCovStats:
         return float(np.diag(self.step_corr, 1).mean())
 
 
-class FullCovHead:
+class FullCovHead(SampledEvals):
+    """The full-covariance head.  Its sampled evaluations (nll.SampledEvals)
+    are GaussianHead's over this head's temporally correlated draws
+    ``sample(pred, seed + i)``, i < k: ``best_of_k`` is
+    g2k_fullcov_best_of_k_f32, ``kde_nll`` g2k_fullcov_kde_nll_f32,
+    ``joint_eval`` g2k_fullcov_joint_eval_f32 (GPU tensors only),
+    ``sample_scores`` g2k_fullcov_sample_scores_f32 and ``sample_modes``
+    g2k_fullcov_sample_modes_f32."""
+    _PREFIX = "g2k_fullcov_"
+    _JOINT_GPU_ONLY = True
+
     def __init__(self, device="cuda"):
         self.chol = torch.eye(DIM, dtype=torch.float32, device=device)
 
@@ -188,16 +197,14 @@ class FullCovHead:
         fc.chol = torch.from_numpy(L.astype(np.float32)).to(device)
         return fc
 
-    def _dims(self, pred):
-        S, F, L2, Nmax = (int(x) for x in pred.shape)
-        if L2 != DIM:
-            raise ValueError(f"pred must be [S, F, {DIM}, Nmax]")
-        return _lib.G2KDims(S, F, OBS_LEN, PRED_LEN, 16, 64, Nmax, OBS_LEN, 0)
-
     def _check_chol(self, dev):
         if tuple(self.chol.shape) != (DIM, DIM):
             raise ValueError(f"chol must be [{DIM}, {DIM}]")
         _check_dev("chol", self.chol, dev, torch.float32)
+
+    def _head_tensor(self, dev):
+        self._check_chol(dev)
+        return self.chol
 
     def _r2(self, levels, dev):
         """[2, NL] float64 on ``dev``: the levels' chi^2(2) radii (a step's
@@ -275,68 +282,3 @@ class FullCovHead:
                                         _stream(stream))
         _lib.check("g2k_fullcov_sample_f32", rc)
         return out
-
-    def best_of_k(self, pred, targets, n_active, k, seed=0, *, n_frames=None, ped_mask=None,
-                  targets_shared=False, want_per_ped=True, want_best=False, stream=None):
-        """Best-of-K in one launch (g2k_fullcov_best_of_k_f32): of the K draws
-        ``sample(pred, seed + i)``, i < k, each pair's smallest ADE and FDE and
-        the draws that attain them -> nll.BestOfK."""
-        d = self._dims(pred)
-        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
-        self._check_chol(pred.device)
-        return _best_of_k("g2k_fullcov_best_of_k_f32", self.chol, d, pred, targets, n_active, k, seed,
-                          n_frames, ped_mask, want_per_ped, want_best, stream)
-
-    def kde_nll(self, pred, targets, n_active, k, seed=0, *, log_floor=-20.0, n_frames=None,
-                ped_mask=None, want_per_ped=False, targets_shared=False, stream=None):
-        """KDE-NLL in one launch (g2k_fullcov_kde_nll_f32): GaussianHead.kde_nll
-        over this head's correlated draws ``sample(pred, seed + i)``, i < k ->
-        nll.KdeNll."""
-        d = self._dims(pred)
-        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
-        self._check_chol(pred.device)
-        return _kde_nll("g2k_fullcov_kde_nll_f32", self.chol, d, pred, targets, n_active, k, seed,
-                        log_floor, n_frames, ped_mask, want_per_ped, stream)
-
-    def sample_scores(self, pred, targets, n_active, k, seed=0, *, n_frames=None, ped_mask=None,
-                      want_per_ped=False, targets_shared=False, stream=None):
-        """Energy, variogram and diversity scores in one launch
-        (g2k_fullcov_sample_scores_f32): GaussianHead.sample_scores over this
-        head's correlated draws ``sample(pred, seed + i)``, i < k ->
-        scores.SampleScores."""
-        from .scores import _sample_scores
-        d = self._dims(pred)
-        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
-        self._check_chol(pred.device)
-        return _sample_scores("g2k_fullcov_sample_scores_f32", self.chol, d, pred, targets, n_active,
-                              k, seed, n_frames, ped_mask, want_per_ped, stream)
-
-    def sample_modes(self, pred, targets, n_active, k, modes, iters=10, seed=0, *, miss_radius=0.0,
-                     n_frames=None, ped_mask=None, want_per_ped=True, want_centres=False,
-                     targets_shared=False, stream=None):
-        """K-means reduction to ``modes`` centres in one launch
-        (g2k_fullcov_sample_modes_f32): GaussianHead.sample_modes over this
-        head's correlated draws ``sample(pred, seed + i)``, i < k ->
-        modes.SampleModes."""
-        from .modes import _sample_modes
-        d = self._dims(pred)
-        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
-        self._check_chol(pred.device)
-        return _sample_modes("g2k_fullcov_sample_modes_f32", self.chol, d, pred, targets, n_active, k,
-                             modes, iters, seed, miss_radius, n_frames, ped_mask, want_per_ped,
-                             want_centres, stream)
-
-    def joint_eval(self, pred, targets, n_active, k, radius, seed=0, *, n_frames=None, ped_mask=None,
-                   targets_shared=False, want_per_frame=True, stream=None):
-        """Joint best-of-K evaluation in one launch (g2k_fullcov_joint_eval_f32):
-        draw i < k of EVERY member of a scene-frame is ``sample(pred, seed +
-        i)``; per scene-frame the smallest mean ADE / FDE over the members
-        (JADE_K / JFDE_K) and the couples that come closer than ``radius`` at
-        any of the 12 predicted steps, in the draws, the mean prediction and the
-        targets -> nll.JointEval (GaussianHead.joint_eval with this head's
-        correlated draws)."""
-        d = self._dims(pred)
-        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
-        self._check_chol(pred.device)
-        return _joint_eval("g2k_fullcov_joint_eval_f32", self.chol, d, pred, targets, n_active, k,
-                           radius, seed, n_frames, ped_mask, want_per_frame, stream, gpu_only=True)

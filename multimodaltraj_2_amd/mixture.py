@@ -28,8 +28,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .frame_step import OBS_LEN, PRED_LEN, _check_dev, _ptr, _stream
-from .nll import _best_of_k, _check_pairs_inputs, _joint_eval, _kde_nll
+from .frame_step import PRED_LEN, _check_dev, _ptr, _stream
+from .nll import SampledEvals, _check_pairs_inputs
 
 DIM = 2 * PRED_LEN
 SLOTS = 8
@@ -59,18 +59,7 @@ SYMBOLS = {
 def load():
     """``_lib.load()``'s handle with this header's symbols bound (once); a
     library without them is an error, there is no fallback."""
-    lib = _lib.load()
-    if not getattr(lib, "_g2k_mix_bound", False):
-        for name, (res, args) in SYMBOLS.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise _lib.G2KLibraryError(f"{_lib.LIB_PATH} does not export {name}: rebuild it "
-                                           "(python __graft_entry__.py)") from e
-            fn.restype = res
-            fn.argtypes = args
-        lib._g2k_mix_bound = True
-    return lib
+    return _lib.bind(_lib.load(), "mix", SYMBOLS)
 
 
 @dataclass
@@ -123,7 +112,18 @@ class MixtureFit:
         return float(self.loglik[-1] - self.loglik[0]) if len(self.loglik) else 0.0
 
 
-class MixtureHead:
+class MixtureHead(SampledEvals):
+    """The Gaussian-mixture head.  Its sampled evaluations (nll.SampledEvals)
+    are FullCovHead's over this head's draws ``sample(pred, seed + i)``, i <
+    k: ``best_of_k`` is g2k_mix_best_of_k_f32, ``kde_nll`` g2k_mix_kde_nll_f32,
+    ``sample_scores`` g2k_mix_sample_scores_f32, ``sample_modes``
+    g2k_mix_sample_modes_f32 and ``joint_eval`` g2k_mix_joint_eval_f32 (GPU
+    tensors only), where each member of a scene-frame draws with the component
+    its own selector picks, so one joint sample mixes components across the
+    pedestrians."""
+    _PREFIX = "g2k_mix_"
+    _JOINT_GPU_ONLY = True
+
     def __init__(self, components=3, device="cuda"):
         components = int(components)
         if not 1 <= components <= SLOTS:
@@ -211,17 +211,18 @@ class MixtureHead:
         return cls.from_block(p, device=dev)
 
     # -- launches -----------------------------------------------------------
-    def _dims(self, pred):
-        S, F, L2, Nmax = (int(x) for x in pred.shape)
-        if L2 != DIM:
-            raise ValueError(f"pred must be [S, F, {DIM}, Nmax]")
-        return _lib.G2KDims(S, F, OBS_LEN, PRED_LEN, 16, 64, Nmax, OBS_LEN, 0)
-
     def _check_params(self, dev, t=None):
         t = self.params if t is None else t
         if tuple(t.shape) != (SLOTS, PITCH):
             raise ValueError(f"params must be [{SLOTS}, {PITCH}]")
         _check_dev("params", t, dev, torch.float32)
+
+    def _head_tensor(self, dev):
+        self._check_params(dev)
+        return self.params
+
+    def _bind(self):
+        load()
 
     def _em_buffers(self, lib, d, dev, rows=1):
         # S = 0 launches nothing: the outputs are the empty launch's zeros
@@ -328,68 +329,3 @@ class MixtureHead:
                                     _stream(stream))
         _lib.check("g2k_mix_sample_f32", rc)
         return (out, comp) if want_components else out
-
-    def best_of_k(self, pred, targets, n_active, k, seed=0, *, n_frames=None, ped_mask=None,
-                  targets_shared=False, want_per_ped=True, want_best=False, stream=None):
-        """Best-of-K in one launch (g2k_mix_best_of_k_f32): of the K draws
-        ``sample(pred, seed + i)``, i < k, each pair's smallest ADE and FDE and
-        the draws that attain them -> nll.BestOfK."""
-        load()
-        d = self._dims(pred)
-        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
-        self._check_params(pred.device)
-        return _best_of_k("g2k_mix_best_of_k_f32", self.params, d, pred, targets, n_active, k, seed,
-                          n_frames, ped_mask, want_per_ped, want_best, stream)
-
-    def kde_nll(self, pred, targets, n_active, k, seed=0, *, log_floor=-20.0, n_frames=None,
-                ped_mask=None, want_per_ped=False, targets_shared=False, stream=None):
-        """KDE-NLL in one launch (g2k_mix_kde_nll_f32): FullCovHead.kde_nll over
-        this head's draws ``sample(pred, seed + i)``, i < k -> nll.KdeNll."""
-        load()
-        d = self._dims(pred)
-        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
-        self._check_params(pred.device)
-        return _kde_nll("g2k_mix_kde_nll_f32", self.params, d, pred, targets, n_active, k, seed,
-                        log_floor, n_frames, ped_mask, want_per_ped, stream)
-
-    def sample_scores(self, pred, targets, n_active, k, seed=0, *, n_frames=None, ped_mask=None,
-                      want_per_ped=False, targets_shared=False, stream=None):
-        """Energy, variogram and diversity scores in one launch
-        (g2k_mix_sample_scores_f32): FullCovHead.sample_scores over this head's
-        draws ``sample(pred, seed + i)``, i < k -> scores.SampleScores."""
-        from .scores import _sample_scores
-        load()
-        d = self._dims(pred)
-        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
-        self._check_params(pred.device)
-        return _sample_scores("g2k_mix_sample_scores_f32", self.params, d, pred, targets, n_active, k,
-                              seed, n_frames, ped_mask, want_per_ped, stream)
-
-    def sample_modes(self, pred, targets, n_active, k, modes, iters=10, seed=0, *, miss_radius=0.0,
-                     n_frames=None, ped_mask=None, want_per_ped=True, want_centres=False,
-                     targets_shared=False, stream=None):
-        """K-means reduction to ``modes`` centres in one launch
-        (g2k_mix_sample_modes_f32): FullCovHead.sample_modes over this head's
-        draws ``sample(pred, seed + i)``, i < k -> modes.SampleModes."""
-        from .modes import _sample_modes
-        load()
-        d = self._dims(pred)
-        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
-        self._check_params(pred.device)
-        return _sample_modes("g2k_mix_sample_modes_f32", self.params, d, pred, targets, n_active, k,
-                             modes, iters, seed, miss_radius, n_frames, ped_mask, want_per_ped,
-                             want_centres, stream)
-
-    def joint_eval(self, pred, targets, n_active, k, radius, seed=0, *, n_frames=None, ped_mask=None,
-                   targets_shared=False, want_per_frame=True, stream=None):
-        """Joint best-of-K evaluation in one launch (g2k_mix_joint_eval_f32):
-        FullCovHead.joint_eval over this head's draws; draw i < k of EVERY
-        member of a scene-frame is ``sample(pred, seed + i)``, each member with
-        the component its own selector picks, so one joint sample mixes
-        components across the pedestrians -> nll.JointEval."""
-        load()
-        d = self._dims(pred)
-        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
-        self._check_params(pred.device)
-        return _joint_eval("g2k_mix_joint_eval_f32", self.params, d, pred, targets, n_active, k,
-                           radius, seed, n_frames, ped_mask, want_per_frame, stream, gpu_only=True)

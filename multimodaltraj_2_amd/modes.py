@@ -21,7 +21,8 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from .frame_step import OBS_LEN, PRED_LEN, _ptr, _stream
+from .frame_step import OBS_LEN, PRED_LEN
+from .nll import _launch
 
 MMAX, KMAX, ITERS_MAX = 32, 256, 64
 GEOM_FIELDS = ("g", "lanes", "fc", "c", "lds_bytes")
@@ -43,18 +44,7 @@ SYMBOLS = {
 def load():
     """``_lib.load()``'s handle with this header's symbols bound (once); a
     library without them is an error, there is no fallback."""
-    lib = _lib.load()
-    if not getattr(lib, "_g2k_modes_bound", False):
-        for name, (res, args) in SYMBOLS.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise _lib.G2KLibraryError(f"{_lib.LIB_PATH} does not export {name}: rebuild it "
-                                           "(python __graft_entry__.py)") from e
-            fn.restype = res
-            fn.argtypes = args
-        lib._g2k_modes_bound = True
-    return lib
+    return _lib.bind(_lib.load(), "modes", SYMBOLS)
 
 
 @dataclass
@@ -156,13 +146,7 @@ def _sample_modes(symbol, head, d, pred, targets, n_active, k, modes, iters, see
     if want_centres:
         centres = torch.empty((S, F, modes, 2 * PRED_LEN, Nmax), dtype=torch.float32, device=dev)
         weights = torch.empty((S, F, modes, Nmax), dtype=torch.float32, device=dev)
-    ws = torch.empty(max(1, int(lib.g2k_sample_modes_workspace_bytes(ctypes.byref(d)))),
-                     dtype=torch.uint8, device=dev)
-    rc = getattr(lib, symbol)(ctypes.byref(d), _ptr(pred), _ptr(targets), _ptr(n_active),
-                              _ptr(n_frames), _ptr(ped_mask), _ptr(head),
-                              ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), k, modes, iters, miss_radius,
-                              _ptr(per_ped), _ptr(centres), _ptr(weights), _ptr(out), _ptr(ws),
-                              ws.numel(), _stream(stream))
-    _lib.check(symbol, rc)
+    _launch(lib, symbol, d, pred, targets, n_active, n_frames, ped_mask, head, seed, stream, k, modes,
+            iters, miss_radius, per_ped, centres, weights, out, size="g2k_sample_modes_workspace_bytes")
     return SampleModes(out=out, per_ped=per_ped, centres=centres, weights=weights, k=k, modes=modes,
                        iters=iters, miss_radius=miss_radius)

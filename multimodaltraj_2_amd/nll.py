@@ -291,100 +291,169 @@ def best_of_k_geometry(S, F, Nmax, k) -> dict:
     return dict(zip(_lib.BESTK_GEOM_FIELDS, (int(v) for v in out)))
 
 
-def _best_of_k(symbol, head, d, pred, targets, n_active, k, seed, n_frames, ped_mask, want_per_ped,
-               want_best, stream):
-    """The marginal best-of-K entry point ``symbol`` (g2k_best_of_k_f32 or
-    g2k_fullcov_best_of_k_f32) on checked inputs; ``head`` is that head's
-    parameter tensor -> BestOfK."""
-    lib = _lib.load()
-    dev = pred.device
-    k = int(k)
-    if not 1 <= k <= 4096:
-        raise ValueError(f"k = {k}: 1..4096")
-    S, F, Nmax = d.S, d.F, d.Nmax
-    sums = torch.empty((S, 8), dtype=torch.float32, device=dev)
-    per_ped = torch.empty((S, F, Nmax, 4), dtype=torch.float32, device=dev) if want_per_ped else None
-    best = torch.empty_like(pred) if want_best else None
-    size = getattr(lib, symbol.replace("_f32", "_workspace_bytes"))
-    ws = torch.empty(max(1, int(size(ctypes.byref(d)))), dtype=torch.uint8, device=dev)
+def _launch(lib, symbol, d, pred, targets, n_active, n_frames, ped_mask, head, seed, stream, *args,
+            size=None):
+    """The tail of every sampled evaluation: the workspace (``size``, the
+    entry point's own ``*_workspace_bytes`` when not named), the seed mod 2^64,
+    the call and its check.  ``args`` are what ``symbol`` takes between the
+    seed and the workspace; tensors and None go as pointers."""
+    size = getattr(lib, size or symbol.replace("_f32", "_workspace_bytes"))
+    ws = torch.empty(max(1, int(size(ctypes.byref(d)))), dtype=torch.uint8, device=pred.device)
+    mid = [_ptr(a) if a is None or isinstance(a, torch.Tensor) else a for a in args]
     rc = getattr(lib, symbol)(ctypes.byref(d), _ptr(pred), _ptr(targets), _ptr(n_active),
                               _ptr(n_frames), _ptr(ped_mask), _ptr(head),
-                              ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), k, _ptr(per_ped), _ptr(best),
-                              _ptr(sums), _ptr(ws), ws.numel(), _stream(stream))
-    _lib.check(symbol, rc)
-    return BestOfK(sums=sums, per_ped=per_ped, best=best)
-
-
-def _kde_nll(symbol, head, d, pred, targets, n_active, k, seed, log_floor, n_frames, ped_mask,
-             want_per_ped, stream):
-    """The KDE-NLL entry point ``symbol`` (g2k_kde_nll_f32 or
-    g2k_fullcov_kde_nll_f32) on checked inputs; ``head`` is that head's
-    parameter tensor -> KdeNll."""
-    lib = _lib.load()
-    dev = pred.device
-    k = int(k)
-    if not 4 <= k <= 4096:
-        raise ValueError(f"k = {k}: 4..4096")
-    log_floor = float(log_floor)
-    if not math.isfinite(log_floor):
-        raise ValueError(f"log_floor = {log_floor}: finite")
-    S, F, Nmax = d.S, d.F, d.Nmax
-    out = torch.empty((S, 8), dtype=torch.float32, device=dev)
-    per_ped = torch.empty((S, F, Nmax, 4), dtype=torch.float32, device=dev) if want_per_ped else None
-    size = getattr(lib, symbol.replace("_f32", "_workspace_bytes"))
-    ws = torch.empty(max(1, int(size(ctypes.byref(d)))), dtype=torch.uint8, device=dev)
-    rc = getattr(lib, symbol)(ctypes.byref(d), _ptr(pred), _ptr(targets), _ptr(n_active),
-                              _ptr(n_frames), _ptr(ped_mask), _ptr(head),
-                              ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), k, ctypes.c_float(log_floor),
-                              _ptr(per_ped), _ptr(out), _ptr(ws), ws.numel(), _stream(stream))
-    _lib.check(symbol, rc)
-    return KdeNll(out=out, per_ped=per_ped, k=k, log_floor=log_floor)
-
-
-def _joint_eval(symbol, head, d, pred, targets, n_active, k, radius, seed, n_frames, ped_mask,
-                want_per_frame, stream, gpu_only=False):
-    """The joint best-of-K entry point ``symbol`` (g2k_joint_eval_f32 or
-    g2k_fullcov_joint_eval_f32) on checked inputs; ``head`` is that head's
-    parameter tensor -> JointEval.  ``gpu_only``: the full-covariance head's
-    wrapper also refuses host tensors (_check_dev only compares devices)."""
-    lib = _lib.load()
-    dev = pred.device
-    k = int(k)
-    if not 1 <= k <= 4096:
-        raise ValueError(f"k = {k}: 1..4096")
-    radius = float(radius)
-    if not (math.isfinite(radius) and radius >= 0.0):
-        raise ValueError(f"radius = {radius}: finite and >= 0")
-    if gpu_only and dev.type != "cuda":
-        raise ValueError(f"pred: on {dev}, expected a GPU tensor")
-    S, F = d.S, d.F
-    sums_f = torch.empty((S, 4), dtype=torch.float32, device=dev)
-    sums_i = torch.empty((S, 6), dtype=torch.int64, device=dev)
-    pf = torch.empty((S, F, 4), dtype=torch.float32, device=dev) if want_per_frame else None
-    pi = torch.empty((S, F, 6), dtype=torch.int32, device=dev) if want_per_frame else None
-    size = getattr(lib, symbol.replace("_f32", "_workspace_bytes"))
-    ws = torch.empty(max(1, int(size(ctypes.byref(d)))), dtype=torch.uint8, device=dev)
-    rc = getattr(lib, symbol)(ctypes.byref(d), _ptr(pred), _ptr(targets), _ptr(n_active),
-                              _ptr(n_frames), _ptr(ped_mask), _ptr(head),
-                              ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), k, ctypes.c_float(radius),
-                              _ptr(pf), _ptr(pi), _ptr(sums_f), _ptr(sums_i), _ptr(ws), ws.numel(),
+                              ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), *mid, _ptr(ws), ws.numel(),
                               _stream(stream))
     _lib.check(symbol, rc)
-    return JointEval(sums_f=sums_f, sums_i=sums_i, per_frame_f=pf, per_frame_i=pi, k=k,
-                     radius=radius)
 
 
-class GaussianHead:
-    def __init__(self, log_sigma=0.0, device="cuda"):
-        h = torch.zeros((3, PRED_LEN), dtype=torch.float32, device=device)
-        h[:2] = float(log_sigma)
-        self.head = h
+class SampledEvals:
+    """The five sampled evaluations of a probabilistic head, once for the three
+    heads (GaussianHead below, fullcov.FullCovHead, mixture.MixtureHead): each
+    is ONE launch over the K draws ``sample(pred, seed + i)``, i < k, of the
+    head it is called on, none of them stored.  A head supplies ``_PREFIX``
+    (its entry points are ``_PREFIX`` + best_of_k_f32, ...), ``_head_tensor``
+    and, where it refuses host tensors in ``joint_eval``, ``_JOINT_GPU_ONLY``;
+    a head whose symbols are bound apart from _lib.SYMBOLS does that in
+    ``_bind``."""
+    _PREFIX = "g2k_"
+    _JOINT_GPU_ONLY = False
+
+    def _head_tensor(self, dev):
+        """The head's parameter tensor, checked (shape, dtype, on ``dev``)."""
+        raise NotImplementedError
+
+    def _bind(self):
+        """Before anything else of an evaluation: the head's own symbols."""
 
     def _dims(self, pred):
         S, F, L2, Nmax = (int(x) for x in pred.shape)
         if L2 != 2 * PRED_LEN:
             raise ValueError(f"pred must be [S, F, {2 * PRED_LEN}, Nmax]")
         return _lib.G2KDims(S, F, OBS_LEN, PRED_LEN, 16, 64, Nmax, OBS_LEN, 0)
+
+    def _sampled_inputs(self, pred, targets, n_active, n_frames, ped_mask, targets_shared):
+        """-> (dims, the head's tensor), everything checked."""
+        self._bind()
+        d = self._dims(pred)
+        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
+        return d, self._head_tensor(pred.device)
+
+    def best_of_k(self, pred, targets, n_active, k, seed=0, *, n_frames=None, ped_mask=None,
+                  targets_shared=False, want_per_ped=True, want_best=False, stream=None):
+        """Best-of-K sampling evaluation in one launch (``_PREFIX`` +
+        best_of_k_f32, csrc/g2k_bestk.hip): of the K draws ``sample(pred, seed
+        + i)``, i < k, each pair's smallest ADE and FDE and the draws that
+        attain them -> BestOfK."""
+        d, head = self._sampled_inputs(pred, targets, n_active, n_frames, ped_mask, targets_shared)
+        lib = _lib.load()
+        dev = pred.device
+        k = int(k)
+        if not 1 <= k <= 4096:
+            raise ValueError(f"k = {k}: 1..4096")
+        S, F, Nmax = d.S, d.F, d.Nmax
+        sums = torch.empty((S, 8), dtype=torch.float32, device=dev)
+        per_ped = torch.empty((S, F, Nmax, 4), dtype=torch.float32, device=dev) if want_per_ped else None
+        best = torch.empty_like(pred) if want_best else None
+        _launch(lib, self._PREFIX + "best_of_k_f32", d, pred, targets, n_active, n_frames, ped_mask,
+                head, seed, stream, k, per_ped, best, sums)
+        return BestOfK(sums=sums, per_ped=per_ped, best=best)
+
+    def kde_nll(self, pred, targets, n_active, k, seed=0, *, log_floor=-20.0, n_frames=None,
+                ped_mask=None, want_per_ped=False, targets_shared=False, stream=None):
+        """KDE-NLL in one launch (``_PREFIX`` + kde_nll_f32, csrc/g2k_kde.hip):
+        per pair and step a Gaussian kernel density estimate (Scott's
+        bandwidth, as scipy.stats.gaussian_kde) of the K draws ``sample(pred,
+        seed + i)``, i < k, and the target's log density under it, floored at
+        ``log_floor`` -> KdeNll.  k in 4..4096."""
+        d, head = self._sampled_inputs(pred, targets, n_active, n_frames, ped_mask, targets_shared)
+        lib = _lib.load()
+        dev = pred.device
+        k = int(k)
+        if not 4 <= k <= 4096:
+            raise ValueError(f"k = {k}: 4..4096")
+        log_floor = float(log_floor)
+        if not math.isfinite(log_floor):
+            raise ValueError(f"log_floor = {log_floor}: finite")
+        S, F, Nmax = d.S, d.F, d.Nmax
+        out = torch.empty((S, 8), dtype=torch.float32, device=dev)
+        per_ped = torch.empty((S, F, Nmax, 4), dtype=torch.float32, device=dev) if want_per_ped else None
+        _launch(lib, self._PREFIX + "kde_nll_f32", d, pred, targets, n_active, n_frames, ped_mask, head,
+                seed, stream, k, log_floor, per_ped, out)
+        return KdeNll(out=out, per_ped=per_ped, k=k, log_floor=log_floor)
+
+    def joint_eval(self, pred, targets, n_active, k, radius, seed=0, *, n_frames=None, ped_mask=None,
+                   targets_shared=False, want_per_frame=True, stream=None):
+        """Joint best-of-K evaluation in one launch (``_PREFIX`` +
+        joint_eval_f32, csrc/g2k_joint.hip): draw i < k of EVERY member of a
+        scene-frame is ``sample(pred, seed + i)``; per scene-frame the smallest
+        mean ADE / FDE over the members (JADE_K / JFDE_K) and the couples that
+        come closer than ``radius`` at any of the 12 predicted steps, in the
+        draws, the mean prediction and the targets -> JointEval."""
+        d, head = self._sampled_inputs(pred, targets, n_active, n_frames, ped_mask, targets_shared)
+        lib = _lib.load()
+        dev = pred.device
+        k = int(k)
+        if not 1 <= k <= 4096:
+            raise ValueError(f"k = {k}: 1..4096")
+        radius = float(radius)
+        if not (math.isfinite(radius) and radius >= 0.0):
+            raise ValueError(f"radius = {radius}: finite and >= 0")
+        # _check_dev only compares devices: the heads that refuse host tensors do it here
+        if self._JOINT_GPU_ONLY and dev.type != "cuda":
+            raise ValueError(f"pred: on {dev}, expected a GPU tensor")
+        S, F = d.S, d.F
+        sums_f = torch.empty((S, 4), dtype=torch.float32, device=dev)
+        sums_i = torch.empty((S, 6), dtype=torch.int64, device=dev)
+        pf = torch.empty((S, F, 4), dtype=torch.float32, device=dev) if want_per_frame else None
+        pi = torch.empty((S, F, 6), dtype=torch.int32, device=dev) if want_per_frame else None
+        _launch(lib, self._PREFIX + "joint_eval_f32", d, pred, targets, n_active, n_frames, ped_mask,
+                head, seed, stream, k, radius, pf, pi, sums_f, sums_i)
+        return JointEval(sums_f=sums_f, sums_i=sums_i, per_frame_f=pf, per_frame_i=pi, k=k,
+                         radius=radius)
+
+    def sample_scores(self, pred, targets, n_active, k, seed=0, *, n_frames=None, ped_mask=None,
+                      want_per_ped=False, targets_shared=False, stream=None):
+        """Energy, variogram and diversity scores of the K draws
+        ``sample(pred, seed + i)``, i < k, in one launch (``_PREFIX`` +
+        sample_scores_f32, csrc/g2k_scores.hip) -> scores.SampleScores.  k in
+        2..256."""
+        from .scores import _sample_scores
+        d, head = self._sampled_inputs(pred, targets, n_active, n_frames, ped_mask, targets_shared)
+        return _sample_scores(self._PREFIX + "sample_scores_f32", head, d, pred, targets, n_active, k,
+                              seed, n_frames, ped_mask, want_per_ped, stream)
+
+    def sample_modes(self, pred, targets, n_active, k, modes, iters=10, seed=0, *, miss_radius=0.0,
+                     n_frames=None, ped_mask=None, want_per_ped=True, want_centres=False,
+                     targets_shared=False, stream=None):
+        """K-means reduction of the K draws ``sample(pred, seed + i)``, i < k,
+        to ``modes`` centres with probabilities and the centres' scores, in one
+        launch (``_PREFIX`` + sample_modes_f32, csrc/g2k_modes.hip) ->
+        modes.SampleModes.  modes in 1..32, k in modes..256, iters in 0..64."""
+        from .modes import _sample_modes
+        d, head = self._sampled_inputs(pred, targets, n_active, n_frames, ped_mask, targets_shared)
+        return _sample_modes(self._PREFIX + "sample_modes_f32", head, d, pred, targets, n_active, k,
+                             modes, iters, seed, miss_radius, n_frames, ped_mask, want_per_ped,
+                             want_centres, stream)
+
+
+class GaussianHead(SampledEvals):
+    """The per-step head.  Its sampled evaluations (SampledEvals) run over the
+    draws of ``sample``, 12 independent steps each: ``best_of_k`` is
+    g2k_best_of_k_f32, ``kde_nll`` g2k_kde_nll_f32, ``joint_eval``
+    g2k_joint_eval_f32 (the one head that does not refuse host tensors there),
+    ``sample_scores`` g2k_sample_scores_f32 and ``sample_modes``
+    g2k_sample_modes_f32."""
+    _PREFIX = "g2k_"
+
+    def __init__(self, log_sigma=0.0, device="cuda"):
+        h = torch.zeros((3, PRED_LEN), dtype=torch.float32, device=device)
+        h[:2] = float(log_sigma)
+        self.head = h
+
+    def _head_tensor(self, dev):
+        _check_dev("head", self.head, dev, torch.float32)
+        return self.head
 
     def nll(self, pred, targets, n_active, *, n_frames=None, ped_mask=None, want_dpred=False,
             stream=None):
@@ -408,71 +477,6 @@ class GaussianHead:
                              _ptr(ws), ws.numel(), _stream(stream))
         _lib.check("g2k_nll_f32", rc)
         return out[3 * PRED_LEN], out[3 * PRED_LEN + 1], out[:3 * PRED_LEN].view(3, PRED_LEN), dpred
-
-    def best_of_k(self, pred, targets, n_active, k, seed=0, *, n_frames=None, ped_mask=None,
-                  targets_shared=False, want_per_ped=True, want_best=False, stream=None):
-        """Best-of-K sampling evaluation in one launch (g2k_best_of_k_f32): of
-        the K draws ``sample(pred, seed + i)``, i < k, each pair's smallest ADE
-        and FDE and the draws that attain them -> BestOfK."""
-        d = self._dims(pred)
-        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
-        _check_dev("head", self.head, pred.device, torch.float32)
-        return _best_of_k("g2k_best_of_k_f32", self.head, d, pred, targets, n_active, k, seed,
-                          n_frames, ped_mask, want_per_ped, want_best, stream)
-
-    def kde_nll(self, pred, targets, n_active, k, seed=0, *, log_floor=-20.0, n_frames=None,
-                ped_mask=None, want_per_ped=False, targets_shared=False, stream=None):
-        """KDE-NLL in one launch (g2k_kde_nll_f32): per pair and step a
-        Gaussian kernel density estimate (Scott's bandwidth, as
-        scipy.stats.gaussian_kde) of the K draws ``sample(pred, seed + i)``,
-        i < k, and the target's log density under it, floored at ``log_floor``
-        -> KdeNll.  k in 4..4096."""
-        d = self._dims(pred)
-        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
-        _check_dev("head", self.head, pred.device, torch.float32)
-        return _kde_nll("g2k_kde_nll_f32", self.head, d, pred, targets, n_active, k, seed, log_floor,
-                        n_frames, ped_mask, want_per_ped, stream)
-
-    def sample_scores(self, pred, targets, n_active, k, seed=0, *, n_frames=None, ped_mask=None,
-                      want_per_ped=False, targets_shared=False, stream=None):
-        """Energy, variogram and diversity scores of the K draws
-        ``sample(pred, seed + i)``, i < k, in one launch (g2k_sample_scores_f32,
-        csrc/g2k_scores.hip) -> scores.SampleScores.  k in 2..256."""
-        from .scores import _sample_scores
-        d = self._dims(pred)
-        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
-        _check_dev("head", self.head, pred.device, torch.float32)
-        return _sample_scores("g2k_sample_scores_f32", self.head, d, pred, targets, n_active, k, seed,
-                              n_frames, ped_mask, want_per_ped, stream)
-
-    def sample_modes(self, pred, targets, n_active, k, modes, iters=10, seed=0, *, miss_radius=0.0,
-                     n_frames=None, ped_mask=None, want_per_ped=True, want_centres=False,
-                     targets_shared=False, stream=None):
-        """K-means reduction of the K draws ``sample(pred, seed + i)``, i < k,
-        to ``modes`` centres with probabilities and the centres' scores, in one
-        launch (g2k_sample_modes_f32, csrc/g2k_modes.hip) -> modes.SampleModes.
-        modes in 1..32, k in modes..256, iters in 0..64."""
-        from .modes import _sample_modes
-        d = self._dims(pred)
-        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
-        _check_dev("head", self.head, pred.device, torch.float32)
-        return _sample_modes("g2k_sample_modes_f32", self.head, d, pred, targets, n_active, k, modes,
-                             iters, seed, miss_radius, n_frames, ped_mask, want_per_ped, want_centres,
-                             stream)
-
-    def joint_eval(self, pred, targets, n_active, k, radius, seed=0, *, n_frames=None, ped_mask=None,
-                   targets_shared=False, want_per_frame=True, stream=None):
-        """Joint best-of-K evaluation in one launch (g2k_joint_eval_f32): draw
-        i < k of EVERY member of a scene-frame is ``sample(pred, seed + i)``;
-        per scene-frame the smallest mean ADE / FDE over the members (JADE_K /
-        JFDE_K) and the couples that come closer than ``radius`` at any of the
-        12 predicted steps, in the draws, the mean prediction and the targets
-        -> JointEval."""
-        d = self._dims(pred)
-        _check_pairs_inputs(d, pred, targets, n_active, n_frames, ped_mask, targets_shared)
-        _check_dev("head", self.head, pred.device, torch.float32)
-        return _joint_eval("g2k_joint_eval_f32", self.head, d, pred, targets, n_active, k, radius,
-                           seed, n_frames, ped_mask, want_per_frame, stream)
 
     def _r2(self, levels, dev):
         """The levels' radii -2 log1p(-p), float64, on ``dev`` (formed on the

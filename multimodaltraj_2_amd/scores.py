@@ -20,7 +20,8 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from .frame_step import OBS_LEN, PRED_LEN, _ptr, _stream
+from .frame_step import OBS_LEN, PRED_LEN
+from .nll import _launch
 
 KMIN, KMAX = 2, 256
 GEOM_FIELDS = ("g", "lanes", "fc", "c", "lds_bytes")
@@ -42,18 +43,7 @@ SYMBOLS = {
 def load():
     """``_lib.load()``'s handle with this header's symbols bound (once); a
     library without them is an error, there is no fallback."""
-    lib = _lib.load()
-    if not getattr(lib, "_g2k_scores_bound", False):
-        for name, (res, args) in SYMBOLS.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise _lib.G2KLibraryError(f"{_lib.LIB_PATH} does not export {name}: rebuild it "
-                                           "(python __graft_entry__.py)") from e
-            fn.restype = res
-            fn.argtypes = args
-        lib._g2k_scores_bound = True
-    return lib
+    return _lib.bind(_lib.load(), "scores", SYMBOLS)
 
 
 @dataclass
@@ -140,11 +130,6 @@ def _sample_scores(symbol, head, d, pred, targets, n_active, k, seed, n_frames, 
     # S = 0 launches nothing: the outputs are the empty launch's zeros
     out = torch.empty((S, 8), dtype=torch.float32, device=dev)
     per_ped = torch.empty((S, F, Nmax, 8), dtype=torch.float32, device=dev) if want_per_ped else None
-    ws = torch.empty(max(1, int(lib.g2k_sample_scores_workspace_bytes(ctypes.byref(d)))),
-                     dtype=torch.uint8, device=dev)
-    rc = getattr(lib, symbol)(ctypes.byref(d), _ptr(pred), _ptr(targets), _ptr(n_active),
-                              _ptr(n_frames), _ptr(ped_mask), _ptr(head),
-                              ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), k, _ptr(per_ped), _ptr(out),
-                              _ptr(ws), ws.numel(), _stream(stream))
-    _lib.check(symbol, rc)
+    _launch(lib, symbol, d, pred, targets, n_active, n_frames, ped_mask, head, seed, stream, k, per_ped,
+            out, size="g2k_sample_scores_workspace_bytes")
     return SampleScores(out=out, per_ped=per_ped, k=k)

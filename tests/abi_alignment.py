@@ -41,7 +41,10 @@ from __future__ import annotations
 
 from dataclasses import dataclass, field
 
-ABI, DATA, SCENE, SCORES = "g2k_abi.hip", "g2k_data.hip", "g2k_scene.hip", "g2k_scores.hip"
+ABI, DATA, SCENE = "g2k_abi.hip", "g2k_data.hip", "g2k_scene.hip"
+# the sampled evaluations' entry points are in the files of their kernels; the
+# checks that their validators share are in one header
+CHECKS, JOINT = "g2k_checks.h", "g2k_joint.hip"
 ELEM_BYTES = {"f32": 4, "i32": 4, "u8": 1, "f64": 8, "i64": 8, "void": 1}
 
 # the three alignment-dependent branches of the scene kernel
@@ -57,9 +60,7 @@ PRED16 = (ABI, "if ((d->flags & G2K_STEP_PRED_PED_MAJOR) && !aligned16(pred))")
 WS4 = (ABI, "if (workspace && !aligned4(workspace))")
 REC16 = (ABI, "if (d->D == kD && (!aligned16(A) || !aligned16(h)))")
 CHAIN16 = (ABI, "if (!aligned16(h) || !aligned16(attn))")
-PERPED16 = (ABI, "if (!joint && (((uintptr_t)out2) & 15))")
-SUMSI8 = (ABI, "if (joint && (((uintptr_t)out2) & 7))")
-SWS4 = (ABI, "if (workspace && (((uintptr_t)workspace) & 3))")
+SUMSI8 = (JOINT, 'if (((uintptr_t)sums_i) & 7) return set_err(G2K_EINVAL, "sums_i must be 8-byte aligned");')
 DBL8 = (ABI, "if ((((uintptr_t)moments) | ((uintptr_t)stats) | ((uintptr_t)inside) | ((uintptr_t)r2)) & 7)")
 STWS8 = (ABI, "if (workspace && (((uintptr_t)workspace) & 7))")
 GATHER8 = (DATA, "if (((uintptr_t)xy & 7u) || ((uintptr_t)pos & 7u) || ((uintptr_t)targets & 7u))")
@@ -71,10 +72,15 @@ EM_DBL8 = (ABI, "if ((((uintptr_t)moments) | ((uintptr_t)resp) | ((uintptr_t)tot
 EM_WS8 = (ABI, 'if (workspace && (((uintptr_t)workspace) & 7))\n'
                '    return set_err(G2K_EINVAL, "workspace must be 8-byte aligned");\n'
                "  const int64_t need = mix_em_ws_bytes(d);")
-# scores_validate
-SC_TGT8 = (SCORES, 'if (((uintptr_t)targets) & 7) return set_err(G2K_EINVAL, "targets must be 8-byte aligned");')
-SC_PERPED16 = (SCORES, 'if (((uintptr_t)per_ped) & 15) return set_err(G2K_EINVAL, "per_ped must be 16-byte aligned");')
-SC_WS4 = (SCORES, "if (workspace && (((uintptr_t)workspace) & 3))")
+# the validators of the sampled evaluations (best-of-K, joint, KDE-NLL, scores):
+# check_targets, check_per_ped and check_workspace, which each of them calls
+# with the bytes of its rows' element (4: floats or int32)
+S_TGT8 = (CHECKS, 'if (((uintptr_t)targets) & 7) return set_err(G2K_EINVAL, "targets must be 8-byte aligned");')
+PERPED16 = (CHECKS, 'if (((uintptr_t)per_ped) & 15) return set_err(G2K_EINVAL, "per_ped must be 16-byte aligned");')
+BK_WS4 = ("g2k_bestk.hip", "check_workspace(d, workspace, workspace_bytes, best_of_k_ws_bytes(d), 4)")
+KDE_WS4 = ("g2k_kde.hip", "check_workspace(d, workspace, workspace_bytes, kde_nll_ws_bytes(d), 4)")
+JT_WS4 = (JOINT, "check_workspace(d, workspace, workspace_bytes, joint_eval_ws_bytes(d), 4,")
+SC_WS4 = ("g2k_scores.hip", "check_workspace(d, workspace, workspace_bytes, scores_ws_bytes(d), 4)")
 
 
 @dataclass(frozen=True)
@@ -227,25 +233,25 @@ def _pairs(head, tgt8=TGT8):
 
 
 def _marginal(name, head):
-    return Entry(name, _pairs(head) + (
+    return Entry(name, _pairs(head, S_TGT8) + (
         Val("seed", 7), Val("K", 20), Arg("per_ped", "f32", 16, "a", PERPED16, note="float4 stores"),
-        c4("best"), c4("out"), Arg("workspace", "void", 4, "a", SWS4, note="float rows"),
+        c4("best"), c4("out"), Arg("workspace", "void", 4, "a", BK_WS4, note="float rows"),
         Val("workspace_bytes", 1 << 30), STREAM), dims=BASE)
 
 
 def _kde(name, head):
-    return Entry(name, _pairs(head) + (
+    return Entry(name, _pairs(head, S_TGT8) + (
         Val("seed", 7), Val("K", 20), Val("log_floor", -20.0),
         Arg("per_ped", "f32", 16, "a", PERPED16, note="float4 stores"), c4("out"),
-        Arg("workspace", "void", 4, "a", SWS4, note="float rows"), Val("workspace_bytes", 1 << 30),
+        Arg("workspace", "void", 4, "a", KDE_WS4, note="float rows"), Val("workspace_bytes", 1 << 30),
         STREAM), dims=BASE)
 
 
 def _joint(name, head):
-    return Entry(name, _pairs(head) + (
+    return Entry(name, _pairs(head, S_TGT8) + (
         Val("seed", 7), Val("K", 20), Val("radius", 0.1), c4("per_frame_f"), c4("per_frame_i", "i32"),
         c4("sums_f"), Arg("sums_i", "i64", 8, "a", SUMSI8),
-        Arg("workspace", "void", 4, "a", SWS4, note="int32 rows"), Val("workspace_bytes", 1 << 30),
+        Arg("workspace", "void", 4, "a", JT_WS4, note="int32 rows"), Val("workspace_bytes", 1 << 30),
         STREAM), dims=BASE)
 
 
@@ -283,8 +289,8 @@ def _dbl8(name):
 
 
 def _scores(name, head):
-    return Entry(name, _pairs(head, SC_TGT8) + (
-        Val("seed", 7), Val("K", 5), Arg("per_ped", "f32", 16, "a", SC_PERPED16, note="two float4 stores a pair"),
+    return Entry(name, _pairs(head, S_TGT8) + (
+        Val("seed", 7), Val("K", 5), Arg("per_ped", "f32", 16, "a", PERPED16, note="two float4 stores a pair"),
         c4("out"), Arg("workspace", "void", 4, "a", SC_WS4, note="float rows"),
         Val("workspace_bytes", 1 << 30), STREAM), dims=BASE)
 
