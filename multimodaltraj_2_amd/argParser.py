@@ -4,8 +4,8 @@ the build's own: --data_root (Q8), --device, --mode,
 --log_dir, --save_dir, --seed, --use_grid_lstm, --loss, --num_samples,
 --sample_seed, --head_log_sigma, --collision_radius, --fit_head,
 --calibration, --fullcov_head, --mixture_head, --mixture_components,
---mixture_iters, --kde_nll, --kde_floor, --sample_scores, --sample_modes,
---modes_draws, --modes_iters, --miss_radius."""
+--mixture_iters, --kde_nll, --kde_floor, --sample_scores, --sample_ranks,
+--rank_bins, --sample_modes, --modes_draws, --modes_iters, --miss_radius."""
 import argparse
 
 
@@ -106,6 +106,15 @@ class ArgsParser:
                              '(24-D norm, ADE, FDE), the expected ADE / FDE of a draw, the average '
                              'pairwise displacement and the variogram score of the K draws, of the '
                              'per-step head and, with --fullcov_head / --mixture_head, of those heads')
+    parser.add_argument('--sample_ranks', type=int, choices=(0, 1), default=0,
+                        help='--num_samples K (4 <= K <= 255): 1 also reports the rank-histogram '
+                             "calibration of the K draws (the target's rank among the draws per step "
+                             'and per trajectory, uniform when calibrated: distance from uniform, '
+                             'mean rank, coverage at 50 / 90 %%), of the per-step head and, with '
+                             '--fullcov_head / --mixture_head, of those heads')
+    parser.add_argument('--rank_bins', type=int, default=0,
+                        help='--sample_ranks: bins of the histograms, a divisor of K + 1 up to 64 '
+                             '(0: the largest divisor <= 32)')
     parser.add_argument('--sample_modes', type=int, default=0,
                         help='--num_samples: M in 1..32 also reduces --modes_draws draws of each head '
                              'in use to M representative trajectories with probabilities (k-means '

@@ -18,7 +18,8 @@ CXX_SRC = sorted(glob.glob(os.path.join(CSRC, "*.cpp")))   # host-only C++ (g++)
 HDR = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(ROOT, "include", "g2k_hip.h"),
                                                       os.path.join(ROOT, "include", "g2k_mix.h"),
                                                       os.path.join(ROOT, "include", "g2k_scores.h"),
-                                                      os.path.join(ROOT, "include", "g2k_modes.h")]
+                                                      os.path.join(ROOT, "include", "g2k_modes.h"),
+                                                      os.path.join(ROOT, "include", "g2k_ranks.h")]
 OUT = os.path.join(HERE, "libg2k_hip.so")
 OBJ = os.path.join(HERE, "build")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

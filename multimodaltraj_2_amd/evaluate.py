@@ -67,9 +67,17 @@ precision), and reports MODES_FIGURES: minADE_M / minFDE_M of the centres,
 their Brier variants with the clusters' weights, the inertia and the number of
 live clusters, and with --miss_radius R > 0 (the dataset's own units, as
 --collision_radius) the share of pairs whose best centre ends farther than R
-from the target.  The units caveat above holds for a pooled fit too: eth_hotel
-is normalised, the UCY sets are world coordinates, so a fold that mixes them
-fits one width to both.  The build's: the reference has no probabilistic head
+from the target.  --sample_ranks 1 (4 <= K <= 255) adds the rank-histogram
+calibration of the same K draws, one g2k_sample_ranks_f32 launch per head in use
+(csrc/g2k_ranks.hip; RANK_FIGURES): the target pooled with the draws and ranked
+among them, per step by a kernel density and per trajectory by the energy
+distance, in --rank_bins bins (0: the largest divisor of K + 1 up to 32) — the
+distance of the histograms from uniform, the mean rank (1/2 when calibrated;
+the steps' above 1/2: the head is too narrow) and the share of targets among
+the 50 / 90 % most typical points: one definition for the three heads, and the
+mixture head's only coverage figure.  The units caveat above holds for a pooled
+fit too: eth_hotel is normalised, the UCY sets are world coordinates, so a fold
+that mixes them fits one width to both.  The build's: the reference has no probabilistic head
 (SURVEY.md §8(f) row 4), so these figures have no reference counterpart.
 """
 from __future__ import annotations
@@ -104,6 +112,10 @@ MODES_FIGURES = ("modes_min_ade", "modes_min_fde", "modes_brier_ade", "modes_bri
                  "modes_live")
 FULLCOV_MODES_FIGURES = tuple("fullcov_" + k for k in MODES_FIGURES)
 MIX_MODES_FIGURES = tuple("mix_" + k for k in MODES_FIGURES)
+RANK_FIGURES = ("rank_dev", "rank_dev_final", "rank_dev_traj", "rank_mean", "rank_mean_traj", "rank_cov50",
+                "rank_nom50", "rank_cov90", "rank_nom90", "rank_degenerate")
+FULLCOV_RANK_FIGURES = tuple("fullcov_" + k for k in RANK_FIGURES)
+MIX_RANK_FIGURES = tuple("mix_" + k for k in RANK_FIGURES)
 
 
 def calib_figures(hs):
@@ -181,6 +193,29 @@ def _modes_line(name, sm, K, dataset, res, prefix=""):
     if sm.miss_radius > 0:
         line += f", miss rate at {sm.miss_radius:g} {res[prefix + 'modes_miss_rate']:.4f}"
     return line
+
+
+def rank_figures(sr, prefix=""):
+    """RANK_FIGURES (``prefix`` "fullcov_": FULLCOV_RANK_FIGURES, "mix_":
+    MIX_RANK_FIGURES) of a ranks.SampleRanks."""
+    nom50, cov50 = sr.coverage(0.5)
+    nom90, cov90 = sr.coverage(0.9)
+    fig = dict(rank_dev=sr.dev, rank_dev_final=sr.dev_final, rank_dev_traj=sr.dev_traj, rank_mean=sr.mean,
+               rank_mean_traj=sr.mean_traj, rank_cov50=cov50, rank_nom50=nom50, rank_cov90=cov90,
+               rank_nom90=nom90, rank_degenerate=sr.degenerate_share)
+    return {prefix + k: fig[k] for k in RANK_FIGURES}
+
+
+def _rank_line(name, sr, dataset, res, prefix=""):
+    """The log line of one head's RANK_FIGURES."""
+    v = {k: res[prefix + k] for k in RANK_FIGURES}
+    return (f"{name} of the {sr.k} draws on dataset {dataset}: {sr.bins} bins, distance from uniform "
+            f"steps {v['rank_dev']:.4f} final step {v['rank_dev_final']:.4f} trajectory "
+            f"{v['rank_dev_traj']:.4f}, mean rank steps {v['rank_mean']:.4f} trajectory "
+            f"{v['rank_mean_traj']:.4f} (1/2 when calibrated; steps above: too narrow), targets among "
+            f"the {v['rank_nom50']:.4f} most typical points {v['rank_cov50']:.4f}, among the "
+            f"{v['rank_nom90']:.4f} most typical {v['rank_cov90']:.4f}, degenerate steps "
+            f"{v['rank_degenerate']:.4f}")
 
 
 def mixture_figures(mx, bk, st, fit):
@@ -270,6 +305,12 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
     those heads' score figures, a log line each that puts minADE_M of the
     centres next to that head's minADE_K (``keep["modes"]``,
     ``keep["fullcov"]["modes"]``, ``keep["mixture"]["modes"]``).
+    --sample_ranks 1 (4 <= K <= 255; --rank_bins) adds RANK_FIGURES from one
+    GaussianHead.sample_ranks launch (csrc/g2k_ranks.hip; same predictions, K
+    and seed) at the end of the per-step head's figures, and
+    FULLCOV_RANK_FIGURES / MIX_RANK_FIGURES at the end of those heads' blocks,
+    a log line each (``keep["ranks"]``, ``keep["fullcov"]["ranks"]``,
+    ``keep["mixture"]["ranks"]``).
     ``keep`` (a dict)
     receives the plan, the predictions, the head and the kernels' outputs for
     a caller that checks them."""
@@ -281,6 +322,17 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
     want_scores = bool(getattr(args, "sample_scores", 0))
     if want_scores and not 2 <= K <= 256:
         raise ValueError("--sample_scores 1 needs --num_samples K with 2 <= K <= 256")
+    want_ranks = bool(getattr(args, "sample_ranks", 0))
+    if want_ranks:
+        from . import ranks as rk
+        if not rk.KMIN <= K <= rk.KMAX:
+            raise ValueError("--sample_ranks 1 needs --num_samples K with 4 <= K <= 255")
+        try:
+            rank_bins = rk.check_k_bins(K, int(getattr(args, "rank_bins", 0) or 0))[1]
+        except ValueError:
+            raise ValueError(f"--rank_bins must be 0 (automatic) or a divisor of K + 1 = {K + 1} in "
+                             f"1..{rk.BMAX}") from None
+        ranks_kw = dict(seed=args.sample_seed, want_per_ped=keep is not None)
     n_modes = int(getattr(args, "sample_modes", 0) or 0)
     if n_modes:
         if not 1 <= n_modes <= 32:
@@ -370,8 +422,14 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
         modes = gh.sample_modes(out.pred, t["targets"], t["n_active"], modes_draws, n_modes, **modes_kw)
         res.update(modes_figures(modes))
         log(_modes_line("sample modes", modes, K, args.leaveDataset, res))
+    ranks = None
+    if want_ranks:
+        ranks = gh.sample_ranks(out.pred, t["targets"], t["n_active"], K, rank_bins, n_frames=one,
+                                ped_mask=t["ped_mask"], **ranks_kw)
+        res.update(rank_figures(ranks))
+        log(_rank_line("sample ranks", ranks, args.leaveDataset, res))
     fc_mode = getattr(args, "fullcov_head", "off") or "off"
-    fc = fc_st = fc_bk = fc_joint = fc_kde = fc_scores = fc_modes = None
+    fc = fc_st = fc_bk = fc_joint = fc_kde = fc_scores = fc_modes = fc_ranks = None
     if fc_mode != "off":
         from .fullcov import FullCovHead
         fc = FullCovHead(device=device)
@@ -429,8 +487,13 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
             res.update(modes_figures(fc_modes, "fullcov_"))
             log(_modes_line("full-covariance sample modes", fc_modes, K, args.leaveDataset, res,
                             "fullcov_"))
+        if want_ranks:
+            fc_ranks = fc.sample_ranks(out.pred, t["targets"], t["n_active"], K, rank_bins, n_frames=one,
+                                       ped_mask=t["ped_mask"], **ranks_kw)
+            res.update(rank_figures(fc_ranks, "fullcov_"))
+            log(_rank_line("full-covariance sample ranks", fc_ranks, args.leaveDataset, res, "fullcov_"))
     mx_mode = getattr(args, "mixture_head", "off") or "off"
-    mx = mx_fit = mx_st = mx_bk = mx_joint = mx_kde = mx_scores = mx_modes = None
+    mx = mx_fit = mx_st = mx_bk = mx_joint = mx_kde = mx_scores = mx_modes = mx_ranks = None
     if mx_mode != "off":
         from .mixture import MixtureHead
         mx = MixtureHead(components=int(getattr(args, "mixture_components", 3)), device=device)
@@ -488,6 +551,11 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                                        **modes_kw)
             res.update(modes_figures(mx_modes, "mix_"))
             log(_modes_line("mixture sample modes", mx_modes, K, args.leaveDataset, res, "mix_"))
+        if want_ranks:
+            mx_ranks = mx.sample_ranks(out.pred, t["targets"], t["n_active"], K, rank_bins, n_frames=one,
+                                       ped_mask=t["ped_mask"], **ranks_kw)
+            res.update(rank_figures(mx_ranks, "mix_"))
+            log(_rank_line("mixture sample ranks", mx_ranks, args.leaveDataset, res, "mix_"))
     if keep is not None:
         keep.update(plan=plan, pred=out.pred, head=gh.head, out=bk, n_frames=np.ones(S, np.int32),
                     joint=joint)
@@ -501,6 +569,8 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                 keep["mixture"]["scores"] = mx_scores
             if mx_modes is not None:
                 keep["mixture"]["modes"] = mx_modes
+            if mx_ranks is not None:
+                keep["mixture"]["ranks"] = mx_ranks
         if calibrate:
             keep.update(calib=calib, fitted=fitted)
         if kde is not None:
@@ -509,6 +579,8 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
             keep.update(scores=scores)
         if modes is not None:
             keep.update(modes=modes)
+        if ranks is not None:
+            keep.update(ranks=ranks)
         if fc is not None:
             keep.update(fullcov=dict(stats=fc_st, out=fc_bk, fitted=ffit), fullcov_chol=fc.chol)
             if fc_joint is not None:
@@ -519,6 +591,8 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                 keep["fullcov"]["scores"] = fc_scores
             if fc_modes is not None:
                 keep["fullcov"]["modes"] = fc_modes
+            if fc_ranks is not None:
+                keep["fullcov"]["ranks"] = fc_ranks
     return res
 
 

@@ -308,7 +308,7 @@ def _launch(lib, symbol, d, pred, targets, n_active, n_frames, ped_mask, head, s
 
 
 class SampledEvals:
-    """The five sampled evaluations of a probabilistic head, once for the three
+    """The six sampled evaluations of a probabilistic head, once for the three
     heads (GaussianHead below, fullcov.FullCovHead, mixture.MixtureHead): each
     is ONE launch over the K draws ``sample(pred, seed + i)``, i < k, of the
     head it is called on, none of them stored.  A head supplies ``_PREFIX``
@@ -436,14 +436,28 @@ class SampledEvals:
                              modes, iters, seed, miss_radius, n_frames, ped_mask, want_per_ped,
                              want_centres, stream)
 
+    def sample_ranks(self, pred, targets, n_active, k, bins=None, seed=0, *, n_frames=None,
+                     ped_mask=None, targets_shared=False, want_per_ped=False, stream=None):
+        """Rank-histogram calibration of the K draws ``sample(pred, seed +
+        i)``, i < k, in one launch (``_PREFIX`` + sample_ranks_f32,
+        csrc/g2k_ranks.hip): the target's rank among the draws per step (a
+        kernel density pre-rank) and per trajectory (an energy pre-rank),
+        uniform when the target comes from the head's law ->
+        ranks.SampleRanks.  k in 4..255; ``bins`` divides k + 1, at most 64
+        (None: the largest divisor <= 32)."""
+        from .ranks import _sample_ranks
+        d, head = self._sampled_inputs(pred, targets, n_active, n_frames, ped_mask, targets_shared)
+        return _sample_ranks(self._PREFIX + "sample_ranks_f32", head, d, pred, targets, n_active, k, bins,
+                             seed, n_frames, ped_mask, want_per_ped, stream)
+
 
 class GaussianHead(SampledEvals):
     """The per-step head.  Its sampled evaluations (SampledEvals) run over the
     draws of ``sample``, 12 independent steps each: ``best_of_k`` is
     g2k_best_of_k_f32, ``kde_nll`` g2k_kde_nll_f32, ``joint_eval``
     g2k_joint_eval_f32 (the one head that does not refuse host tensors there),
-    ``sample_scores`` g2k_sample_scores_f32 and ``sample_modes``
-    g2k_sample_modes_f32."""
+    ``sample_scores`` g2k_sample_scores_f32, ``sample_modes``
+    g2k_sample_modes_f32 and ``sample_ranks`` g2k_sample_ranks_f32."""
     _PREFIX = "g2k_"
 
     def __init__(self, log_sigma=0.0, device="cuda"):

@@ -52,6 +52,8 @@
   scores, one g2k_sample_scores_f32 launch; with --sample_modes M also the
   k-means reduction of --modes_draws draws to M centres and the centres'
   minADE_M / minFDE_M, Brier variants and miss rate, one g2k_sample_modes_f32
+  launch per head in use; with --sample_ranks 1 also the rank-histogram
+  calibration of the K draws in --rank_bins bins, one g2k_sample_ranks_f32
   launch per head in use).
 
 The model weights are one seeded N(0, 1) draw (quirk Q15: the reference
