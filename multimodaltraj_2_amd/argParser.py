@@ -5,7 +5,8 @@ the build's own: --data_root (Q8), --device, --mode,
 --sample_seed, --head_log_sigma, --collision_radius, --fit_head,
 --calibration, --fullcov_head, --mixture_head, --mixture_components,
 --mixture_iters, --kde_nll, --kde_floor, --sample_scores, --sample_ranks,
---rank_bins, --sample_modes, --modes_draws, --modes_iters, --miss_radius."""
+--rank_bins, --sample_kinematics, --kin_bins, --sample_modes, --modes_draws,
+--modes_iters, --miss_radius."""
 import argparse
 
 
@@ -115,6 +116,16 @@ class ArgsParser:
     parser.add_argument('--rank_bins', type=int, default=0,
                         help='--sample_ranks: bins of the histograms, a divisor of K + 1 up to 64 '
                              '(0: the largest divisor <= 32)')
+    parser.add_argument('--sample_kinematics', type=int, choices=(0, 1), default=0,
+                        help='--num_samples K (2 <= K <= 255): 1 also reports the kinematic scores of '
+                             'the K draws (per group of features, speed / acc / lacc / straight in the '
+                             "dataset's units per step: the fair CRPS, the target's mean PIT rank among "
+                             "the draws, the PIT histogram's distance from uniform, the draws' and the "
+                             "targets' mean feature), of the per-step head and, with --fullcov_head / "
+                             '--mixture_head, of those heads')
+    parser.add_argument('--kin_bins', type=int, default=0,
+                        help='--sample_kinematics: bins of the PIT histograms, a divisor of K + 1 up to '
+                             '64 (0: the largest divisor <= 32)')
     parser.add_argument('--sample_modes', type=int, default=0,
                         help='--num_samples: M in 1..32 also reduces --modes_draws draws of each head '
                              'in use to M representative trajectories with probabilities (k-means '

@@ -75,7 +75,14 @@ distance, in --rank_bins bins (0: the largest divisor of K + 1 up to 32) — the
 distance of the histograms from uniform, the mean rank (1/2 when calibrated;
 the steps' above 1/2: the head is too narrow) and the share of targets among
 the 50 / 90 % most typical points: one definition for the three heads, and the
-mixture head's only coverage figure.  The units caveat above holds for a pooled
+mixture head's only coverage figure.  --sample_kinematics 1 (2 <= K <= 255) adds
+the kinematic scores of the same K draws, one g2k_sample_kin_f32 launch per head
+in use (csrc/g2k_kin.hip; KIN_FIGURES): per group of features — speed, acc,
+lacc (longitudinal acceleration) and straight, in the dataset's units per 0.4 s
+step — the fair CRPS, the mean PIT rank of the target among the draws (1/2 when
+calibrated; below it: the draws' feature is larger than the target's), the
+distance of the PIT histogram from uniform in --kin_bins bins, and the draws'
+and the targets' mean feature.  The units caveat above holds for a pooled
 fit too: eth_hotel is normalised, the UCY sets are world coordinates, so a fold
 that mixes them fits one width to both.  The build's: the reference has no probabilistic head
 (SURVEY.md §8(f) row 4), so these figures have no reference counterpart.
@@ -116,6 +123,10 @@ RANK_FIGURES = ("rank_dev", "rank_dev_final", "rank_dev_traj", "rank_mean", "ran
                 "rank_nom50", "rank_cov90", "rank_nom90", "rank_degenerate")
 FULLCOV_RANK_FIGURES = tuple("fullcov_" + k for k in RANK_FIGURES)
 MIX_RANK_FIGURES = tuple("mix_" + k for k in RANK_FIGURES)
+KIN_GROUPS = ("speed", "acc", "lacc", "straight")
+KIN_FIGURES = tuple(f"kin_{f}_{g}" for f in ("crps", "pit", "dev", "draw", "target") for g in KIN_GROUPS)
+FULLCOV_KIN_FIGURES = tuple("fullcov_" + k for k in KIN_FIGURES)
+MIX_KIN_FIGURES = tuple("mix_" + k for k in KIN_FIGURES)
 
 
 def calib_figures(hs):
@@ -218,6 +229,25 @@ def _rank_line(name, sr, dataset, res, prefix=""):
             f"{v['rank_degenerate']:.4f}")
 
 
+def kin_figures(sk, prefix=""):
+    """KIN_FIGURES (``prefix`` "fullcov_": FULLCOV_KIN_FIGURES, "mix_":
+    MIX_KIN_FIGURES) of a kin.SampleKin."""
+    fig = {}
+    for g in KIN_GROUPS:
+        fig.update({f"kin_crps_{g}": sk.crps(g), f"kin_pit_{g}": sk.pit_mean(g), f"kin_dev_{g}": sk.dev(g),
+                    f"kin_draw_{g}": sk.draw_mean(g), f"kin_target_{g}": sk.target_mean(g)})
+    return {prefix + k: fig[k] for k in KIN_FIGURES}
+
+
+def _kin_line(name, sk, dataset, res, prefix=""):
+    """The log line of one head's KIN_FIGURES."""
+    parts = [f"{g} crps {res[prefix + 'kin_crps_' + g]:.4f} pit {res[prefix + 'kin_pit_' + g]:.4f} "
+             f"dev {res[prefix + 'kin_dev_' + g]:.4f} draws {res[prefix + 'kin_draw_' + g]:.4f} "
+             f"targets {res[prefix + 'kin_target_' + g]:.4f}" for g in KIN_GROUPS]
+    return (f"{name} of the {sk.k} draws on dataset {dataset}: {sk.bins} bins (pit 1/2 when calibrated; "
+            f"below: the draws' feature is the larger), " + ", ".join(parts))
+
+
 def mixture_figures(mx, bk, st, fit):
     """MIX_FIGURES of a fitted MixtureHead: its best-of-K result and
     MixtureStats on the evaluated scenes, and the MixtureFit that made it
@@ -311,6 +341,11 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
     FULLCOV_RANK_FIGURES / MIX_RANK_FIGURES at the end of those heads' blocks,
     a log line each (``keep["ranks"]``, ``keep["fullcov"]["ranks"]``,
     ``keep["mixture"]["ranks"]``).
+    --sample_kinematics 1 (2 <= K <= 255; --kin_bins) adds KIN_FIGURES from one
+    GaussianHead.sample_kin launch (csrc/g2k_kin.hip; same predictions, K and
+    seed) after the rank figures, and FULLCOV_KIN_FIGURES / MIX_KIN_FIGURES at
+    the end of those heads' blocks, a log line each (``keep["kin"]``,
+    ``keep["fullcov"]["kin"]``, ``keep["mixture"]["kin"]``).
     ``keep`` (a dict)
     receives the plan, the predictions, the head and the kernels' outputs for
     a caller that checks them."""
@@ -333,6 +368,17 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
             raise ValueError(f"--rank_bins must be 0 (automatic) or a divisor of K + 1 = {K + 1} in "
                              f"1..{rk.BMAX}") from None
         ranks_kw = dict(seed=args.sample_seed, want_per_ped=keep is not None)
+    want_kin = bool(getattr(args, "sample_kinematics", 0))
+    if want_kin:
+        from . import kin as kn
+        if not kn.KMIN <= K <= kn.KMAX:
+            raise ValueError("--sample_kinematics 1 needs --num_samples K with 2 <= K <= 255")
+        try:
+            kin_bins = kn.check_k_bins(K, int(getattr(args, "kin_bins", 0) or 0))[1]
+        except ValueError:
+            raise ValueError(f"--kin_bins must be 0 (automatic) or a divisor of K + 1 = {K + 1} in "
+                             f"1..{kn.BMAX}") from None
+        kin_kw = dict(seed=args.sample_seed, want_per_ped=keep is not None)
     n_modes = int(getattr(args, "sample_modes", 0) or 0)
     if n_modes:
         if not 1 <= n_modes <= 32:
@@ -428,8 +474,14 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                                 ped_mask=t["ped_mask"], **ranks_kw)
         res.update(rank_figures(ranks))
         log(_rank_line("sample ranks", ranks, args.leaveDataset, res))
+    kin = None
+    if want_kin:
+        kin = gh.sample_kin(out.pred, t["targets"], t["n_active"], K, kin_bins, n_frames=one,
+                            ped_mask=t["ped_mask"], **kin_kw)
+        res.update(kin_figures(kin))
+        log(_kin_line("sample kinematics", kin, args.leaveDataset, res))
     fc_mode = getattr(args, "fullcov_head", "off") or "off"
-    fc = fc_st = fc_bk = fc_joint = fc_kde = fc_scores = fc_modes = fc_ranks = None
+    fc = fc_st = fc_bk = fc_joint = fc_kde = fc_scores = fc_modes = fc_ranks = fc_kin = None
     if fc_mode != "off":
         from .fullcov import FullCovHead
         fc = FullCovHead(device=device)
@@ -492,8 +544,13 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                                        ped_mask=t["ped_mask"], **ranks_kw)
             res.update(rank_figures(fc_ranks, "fullcov_"))
             log(_rank_line("full-covariance sample ranks", fc_ranks, args.leaveDataset, res, "fullcov_"))
+        if want_kin:
+            fc_kin = fc.sample_kin(out.pred, t["targets"], t["n_active"], K, kin_bins, n_frames=one,
+                                   ped_mask=t["ped_mask"], **kin_kw)
+            res.update(kin_figures(fc_kin, "fullcov_"))
+            log(_kin_line("full-covariance sample kinematics", fc_kin, args.leaveDataset, res, "fullcov_"))
     mx_mode = getattr(args, "mixture_head", "off") or "off"
-    mx = mx_fit = mx_st = mx_bk = mx_joint = mx_kde = mx_scores = mx_modes = mx_ranks = None
+    mx = mx_fit = mx_st = mx_bk = mx_joint = mx_kde = mx_scores = mx_modes = mx_ranks = mx_kin = None
     if mx_mode != "off":
         from .mixture import MixtureHead
         mx = MixtureHead(components=int(getattr(args, "mixture_components", 3)), device=device)
@@ -556,6 +613,11 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                                        ped_mask=t["ped_mask"], **ranks_kw)
             res.update(rank_figures(mx_ranks, "mix_"))
             log(_rank_line("mixture sample ranks", mx_ranks, args.leaveDataset, res, "mix_"))
+        if want_kin:
+            mx_kin = mx.sample_kin(out.pred, t["targets"], t["n_active"], K, kin_bins, n_frames=one,
+                                   ped_mask=t["ped_mask"], **kin_kw)
+            res.update(kin_figures(mx_kin, "mix_"))
+            log(_kin_line("mixture sample kinematics", mx_kin, args.leaveDataset, res, "mix_"))
     if keep is not None:
         keep.update(plan=plan, pred=out.pred, head=gh.head, out=bk, n_frames=np.ones(S, np.int32),
                     joint=joint)
@@ -571,6 +633,8 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                 keep["mixture"]["modes"] = mx_modes
             if mx_ranks is not None:
                 keep["mixture"]["ranks"] = mx_ranks
+            if mx_kin is not None:
+                keep["mixture"]["kin"] = mx_kin
         if calibrate:
             keep.update(calib=calib, fitted=fitted)
         if kde is not None:
@@ -581,6 +645,8 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
             keep.update(modes=modes)
         if ranks is not None:
             keep.update(ranks=ranks)
+        if kin is not None:
+            keep.update(kin=kin)
         if fc is not None:
             keep.update(fullcov=dict(stats=fc_st, out=fc_bk, fitted=ffit), fullcov_chol=fc.chol)
             if fc_joint is not None:
@@ -593,6 +659,8 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                 keep["fullcov"]["modes"] = fc_modes
             if fc_ranks is not None:
                 keep["fullcov"]["ranks"] = fc_ranks
+            if fc_kin is not None:
+                keep["fullcov"]["kin"] = fc_kin
     return res
 
 

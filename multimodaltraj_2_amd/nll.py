@@ -308,7 +308,7 @@ def _launch(lib, symbol, d, pred, targets, n_active, n_frames, ped_mask, head, s
 
 
 class SampledEvals:
-    """The six sampled evaluations of a probabilistic head, once for the three
+    """The seven sampled evaluations of a probabilistic head, once for the three
     heads (GaussianHead below, fullcov.FullCovHead, mixture.MixtureHead): each
     is ONE launch over the K draws ``sample(pred, seed + i)``, i < k, of the
     head it is called on, none of them stored.  A head supplies ``_PREFIX``
@@ -450,6 +450,19 @@ class SampledEvals:
         return _sample_ranks(self._PREFIX + "sample_ranks_f32", head, d, pred, targets, n_active, k, bins,
                              seed, n_frames, ped_mask, want_per_ped, stream)
 
+    def sample_kin(self, pred, targets, n_active, k, bins=None, seed=0, *, n_frames=None,
+                   ped_mask=None, targets_shared=False, want_per_ped=False, stream=None):
+        """Kinematic scores of the K draws ``sample(pred, seed + i)``, i < k,
+        in one launch (``_PREFIX`` + sample_kin_f32, csrc/g2k_kin.hip): per
+        group of features (speed, acc, lacc, straight) the fair CRPS and the
+        target's PIT rank among the draws, uniform when the target moves as
+        the head's draws do -> kin.SampleKin.  k in 2..255; ``bins`` divides
+        k + 1, at most 64 (None: the largest divisor <= 32)."""
+        from .kin import _sample_kin
+        d, head = self._sampled_inputs(pred, targets, n_active, n_frames, ped_mask, targets_shared)
+        return _sample_kin(self._PREFIX + "sample_kin_f32", head, d, pred, targets, n_active, k, bins,
+                           seed, n_frames, ped_mask, want_per_ped, stream)
+
 
 class GaussianHead(SampledEvals):
     """The per-step head.  Its sampled evaluations (SampledEvals) run over the
@@ -457,7 +470,8 @@ class GaussianHead(SampledEvals):
     g2k_best_of_k_f32, ``kde_nll`` g2k_kde_nll_f32, ``joint_eval``
     g2k_joint_eval_f32 (the one head that does not refuse host tensors there),
     ``sample_scores`` g2k_sample_scores_f32, ``sample_modes``
-    g2k_sample_modes_f32 and ``sample_ranks`` g2k_sample_ranks_f32."""
+    g2k_sample_modes_f32, ``sample_ranks`` g2k_sample_ranks_f32 and
+    ``sample_kin`` g2k_sample_kin_f32."""
     _PREFIX = "g2k_"
 
     def __init__(self, log_sigma=0.0, device="cuda"):

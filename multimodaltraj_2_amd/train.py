@@ -54,7 +54,9 @@
   minADE_M / minFDE_M, Brier variants and miss rate, one g2k_sample_modes_f32
   launch per head in use; with --sample_ranks 1 also the rank-histogram
   calibration of the K draws in --rank_bins bins, one g2k_sample_ranks_f32
-  launch per head in use).
+  launch per head in use; with --sample_kinematics 1 also the kinematic scores
+  of the K draws in --kin_bins bins, one g2k_sample_kin_f32 launch per head in
+  use).
 
 The model weights are one seeded N(0, 1) draw (quirk Q15: the reference
 re-draws them every batch), padded to Nmax (8 for the node slice).
