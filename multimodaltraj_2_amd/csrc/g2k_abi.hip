@@ -9,6 +9,7 @@
 
 #include "g2k_common.h"
 #include "g2k_mix.h"
+#include "g2k_step_fixed.h"
 
 namespace g2k {
 
@@ -246,6 +247,17 @@ int g2k_step_geometry(const g2k_dims* d, int32_t train, int32_t has_h_in, int32_
   g2k_dims x = *d;
   if (split_automatic(x)) x.flags |= G2K_STEP_SPLIT(scene_split_cus(x, cus));
   return scene_geometry(x, train != 0, has_h_in != 0, out);
+}
+
+// include/g2k_step_fixed.h (added after ABI 11): the checks of g2k_step_geometry
+int g2k_step_fixed_geometry(const g2k_dims* d, int32_t train, int32_t has_h_in, int32_t cus,
+                            int32_t* out) {
+  int32_t geom[G2K_GEOM_FIELDS];
+  const int rc = g2k_step_geometry(d, train, has_h_in, cus, out ? geom : nullptr);
+  if (rc) return rc;
+  g2k_dims x = *d;
+  if (split_automatic(x)) x.flags |= G2K_STEP_SPLIT(scene_split_cus(x, cus));
+  return scene_fixed_geometry(x, train != 0, has_h_in != 0, out);
 }
 
 int64_t g2k_step_workspace_bytes(const g2k_dims* d) {

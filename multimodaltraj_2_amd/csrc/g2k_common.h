@@ -498,6 +498,9 @@ int64_t scene_lds_bytes(const g2k_dims* d, bool grad);
 // what scene_step_launch would build for `d` (g2k_step_geometry: out[G2K_GEOM_FIELDS]);
 // `d` carries an explicit split.  Host arithmetic only: no HIP call.
 int scene_geometry(const g2k_dims& d, bool grad, bool has_h_in, int32_t* out);
+// the same launch's fixed-frame build and residency (g2k_step_fixed_geometry:
+// out[G2K_STEP_FIXED_FIELDS], include/g2k_step_fixed.h).  Host arithmetic only.
+int scene_fixed_geometry(const g2k_dims& d, bool grad, bool has_h_in, int32_t* out);
 
 // floats of one parameter vector (g2k_grad_size): + the NLL head [3][12]
 constexpr int kNllHead = 3 * kL;

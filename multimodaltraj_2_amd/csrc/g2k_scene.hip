@@ -26,6 +26,7 @@
 // by g2k_grad_rows_kernel (g2k_train.hip) in a fixed order.
 #include "g2k_common.h"
 #include "g2k_recur.h"
+#include "g2k_step_fixed.h"
 
 namespace g2k {
 namespace {
@@ -33,6 +34,10 @@ namespace {
 constexpr int kSceneChunk = 32;
 constexpr int kRecW = 4;
 constexpr int64_t kCoresidentLds = 80 * 1024;   // G2K_STEP_CORESIDENT: two workgroups' LDS per CU
+// The model's own frame count, obs_len + pred_len: the co-resident forward
+// step has a build with F, the chunk length and stride 1 as compile-time
+// constants (g2k_scene_kernel<..., FX>, scene_fixed)
+constexpr int kFixedFrames = kT + kL;
 // small block of weights / per-scene matrices in LDS (floats)
 constexpr int SM_WII = 0;     // [16][8]
 constexpr int SM_WV = 128;    // [8][18]
@@ -91,7 +96,8 @@ struct SceneLayout {
 };
 
 __host__ __device__ inline SceneLayout scene_layout_fc(int Nmax, int stride, int F, int fc, int NP,
-                                                       bool grad, bool nll = false, bool inv = false) {
+                                                       bool grad, bool nll = false, bool inv = false,
+                                                       bool alias_pos = false) {
   SceneLayout s;
   s.fc = fc;
   s.split = 1;
@@ -116,7 +122,17 @@ __host__ __device__ inline SceneLayout scene_layout_fc(int Nmax, int stride, int
   s.o_flag = o;  o += rup4(fc);                      // As ring flags (recurrence polls)
   s.o_mflag = o; o += rup4(fc);                      // M ring flags (prediction tiles poll)
   s.o_red = o;   o += 4 * 16 * kRecW;
-  s.o_pos = o;   o += s.wcmax * s.pp;                  // raw position window (LDS-DMA)
+  // raw position window (LDS-DMA).  alias_pos (the fixed-frame forward build:
+  // one chunk, no train-mode reader of the window): the window shares the
+  // start of the As ring's space when it is no larger than the ring.  The
+  // window's life ends before the ring's begins, with a workgroup barrier
+  // between: DMA issue (kernel entry) -> vmcnt(0), B1 -> scene_vtile, the
+  // window's only reader (producer waves, between B1 and B2) -> lgkmcnt(0),
+  // B2 -> the first ring write (frame_head of either role, after scene_stage
+  // returns).  One chunk: no later DMA writes the window again.
+  const bool alias = alias_pos && s.wcmax * s.pp <= slots * kD * kD;
+  s.o_pos = alias ? s.o_ring : o;
+  o += alias ? 0 : s.wcmax * s.pp;
   // VG = V @ g: window, Ve0, Ve1, bv rows [.][8] (PAD: [.][16], columns 8..15
   // zero, and a zero row)
   s.o_vg = o;    o += pad ? (s.wcmax + 4) * kD : rup4((s.wcmax + 3) * kT);
@@ -139,6 +155,18 @@ __host__ __device__ inline SceneLayout scene_layout_fc(int Nmax, int stride, int
     s.o_nllc = o;   o += nll ? 5 * kL : 0;
   }
   s.total = o;
+  return s;
+}
+
+// The fixed-frame forward build's layout (g2k_scene_kernel<..., FX>): what
+// scene_layout gives a stride-1, one-workgroup-per-scene forward launch of FX
+// frames in one chunk, with the position window aliased onto the As ring
+// (scene_layout_fc) so that the scene's LDS fits a CU three times at Nmax 32 —
+// formed again in the kernel from Nmax, so that every offset is FX-constant
+// arithmetic (tfb: the launch's, G2K_STEP_TARGETS_SHARED)
+__host__ __device__ inline SceneLayout scene_layout_fixed(int Nmax, int FX, int NP, int tfb) {
+  SceneLayout s = scene_layout_fc(Nmax, 1, FX, FX, NP, false, false, false, /*alias_pos=*/true);
+  s.tfb = tfb;
   return s;
 }
 
@@ -1903,13 +1931,25 @@ __device__ __forceinline__ void rec_grad_work(const StepArgs& a, const SceneLayo
 // workgroup (NP = 4 below H 512) is sized for two co-resident workgroups per
 // CU (4 waves per SIMD, <= 128 VGPRs), so the next launch's scenes start on a
 // CU while this launch's recurrence waves finish their chain.
-template <int TPW, int NP>
-constexpr int scene_waves_per_eu() { return NP == 4 && TPW < 8 ? 4 : 1; }
+// The fixed-frame build (FX > 0) below H 256: three workgroups per CU (6
+// waves per SIMD, <= 80 VGPRs; it needs 74 and spills nothing).  Its H 256
+// build needs 90 (held to 80 it spills 7): two per CU, as before.
+constexpr int kFixedTpw3 = 4;   // TPW below which the fixed build runs three per CU
+template <int TPW, int NP, int FX = 0>
+constexpr int scene_waves_per_eu() {
+  return FX > 0 && TPW < kFixedTpw3 ? 6 : (NP == 4 && TPW < 8 ? 4 : 1);
+}
 
-template <int TPW, int NP, bool GRAD, bool PM, bool NLL, bool INV, bool BLK = false>
+// FX > 0 (scene_fixed: forward, the co-resident geometry, the general variant,
+// one workgroup per scene): F = fc = FX and stride 1 are compile-time
+// constants — one chunk, so the chunk loops, their re-staging and B3 fold
+// away and the layout's offsets depend on Nmax alone.  Nmax, H, W, n_active,
+// n_frames and ped_mask stay runtime values; the code is the general kernel's.
+template <int TPW, int NP, bool GRAD, bool PM, bool NLL, bool INV, bool BLK = false, int FX = 0>
 __global__ void __launch_bounds__(64 * (kRecW + NP))
-__attribute__((amdgpu_waves_per_eu(scene_waves_per_eu<TPW, NP>())))
+__attribute__((amdgpu_waves_per_eu(scene_waves_per_eu<TPW, NP, FX>())))
 g2k_scene_kernel(StepArgs a, SceneLayout lay) {
+  static_assert(FX == 0 || (!GRAD && !NLL && !INV && !BLK && NP == 4 && TPW < 8), "fixed-frame build");
   constexpr int NT = 64 * (kRecW + NP);
   constexpr int kRB = 16 * kRecW;
   // the co-resident geometry (8 waves, two workgroups per CU, forward only):
@@ -1921,9 +1961,17 @@ g2k_scene_kernel(StepArgs a, SceneLayout lay) {
   // every kernel-argument line the prologue reads, in ONE scalar-load round
   // trip (left alone, the compiler asks for the n_active / h_in line only
   // after the first batch has landed: a second dependent kernarg miss)
-  asm volatile("" ::"s"(a.pos), "s"(a.vislet), "s"(a.G), "s"(a.n_active), "s"(a.n_frames),
-               "s"(a.h_in), "s"(a.w.Wi), "s"(a.w.Wo), "s"(a.d.Nmax), "s"(a.d.F), "s"(a.d.W),
-               "s"(a.d.stride), "s"(lay.fc), "s"(lay.pp), "s"(lay.o_pos));
+  if constexpr (FX > 0) {
+    asm volatile("" ::"s"(a.pos), "s"(a.vislet), "s"(a.G), "s"(a.n_active), "s"(a.n_frames),
+                 "s"(a.h_in), "s"(a.w.Wi), "s"(a.w.Wo), "s"(a.d.Nmax), "s"(a.d.W), "s"(lay.tfb));
+    a.d.F = FX;
+    a.d.stride = 1;
+    lay = scene_layout_fixed(a.d.Nmax, FX, NP, lay.tfb);   // (the host's layout: scene_plan)
+  } else {
+    asm volatile("" ::"s"(a.pos), "s"(a.vislet), "s"(a.G), "s"(a.n_active), "s"(a.n_frames),
+                 "s"(a.h_in), "s"(a.w.Wi), "s"(a.w.Wo), "s"(a.d.Nmax), "s"(a.d.F), "s"(a.d.W),
+                 "s"(a.d.stride), "s"(lay.fc), "s"(lay.pp), "s"(lay.o_pos));
+  }
   SceneCtx c;
   c.X = lay.split;
   c.s = lay.split == 1 ? (int)blockIdx.x : (int)blockIdx.x / lay.split;
@@ -2060,10 +2108,27 @@ inline int scene_variant(const g2k_dims& d, const SceneLayout& l, bool grad) {
   return G2K_STEP_VARIANT_GENERAL;
 }
 
+// The fixed-frame build (g2k_scene_kernel<..., kFixedFrames>) serves exactly:
+// the forward step in the co-resident geometry (4 producers below H 512), the
+// general variant, stride 1, one workgroup per scene, F = 20 frames in one
+// chunk.  Everything else takes the unspecialised builds.
+inline bool scene_fixed(const g2k_dims& d, const SceneLayout& l, int NP, int tpw, bool grad) {
+  return !grad && NP == 4 && tpw < 8 && d.stride == 1 && d.F == kFixedFrames &&
+         l.fc == kFixedFrames && l.split == 1 && l.own0 == 0 &&
+         scene_variant(d, l, false) == G2K_STEP_VARIANT_GENERAL;
+}
+
 template <int TPW, int NP, bool GRAD, bool PM>
 void launch_kp(const StepArgs& a, const SceneLayout& l, hipStream_t st) {
   const dim3 grid(a.d.S * l.split), block(64 * (kRecW + NP));
   const size_t lds = (size_t)l.total * 4;
+  if constexpr (!GRAD && NP == 4 && TPW < 8) {
+    if (scene_fixed(a.d, l, NP, TPW, GRAD)) {
+      hipLaunchKernelGGL((g2k_scene_kernel<TPW, NP, false, PM, false, false, false, kFixedFrames>), grid,
+                         block, lds, st, a, l);
+      return;
+    }
+  }
   switch (scene_variant(a.d, l, GRAD)) {
     case G2K_STEP_VARIANT_NLL:
       hipLaunchKernelGGL((g2k_scene_kernel<TPW, NP, GRAD, PM, GRAD, false>), grid, block, lds, st, a, l);
@@ -2118,11 +2183,16 @@ int launch_np(const StepArgs& a, const SceneLayout& l, int NP, int tpw, hipStrea
   return set_err(G2K_EUNSUPPORTED, "scene kernel not built for H=%d (NP=%d)", a.d.H, NP);
 }
 
+// the layout a launch uses: scene_layout, or the fixed-frame build's own
+SceneLayout scene_launch_layout(const g2k_dims& d, int NP, int tpw, bool grad) {
+  const SceneLayout l = scene_layout(&d, NP, grad);
+  return scene_fixed(d, l, NP, tpw, grad) ? scene_layout_fixed(d.Nmax, kFixedFrames, NP, l.tfb) : l;
+}
 }  // namespace
 
 int64_t scene_lds_bytes(const g2k_dims* d, bool grad) {
   const int H = grad && d->H < 64 ? 64 : d->H;
-  return (int64_t)scene_layout(d, scene_producers(*d, H, grad), grad).total * 4;
+  return (int64_t)scene_launch_layout(*d, scene_producers(*d, H, grad), H / 64, grad).total * 4;
 }
 
 namespace {
@@ -2137,8 +2207,8 @@ ScenePlan scene_plan(const g2k_dims& d, bool grad, bool has_h_in) {
   ScenePlan p;
   p.H = has_h_in ? d.H : 64;
   p.NP = scene_producers(d, p.H, grad);
-  p.l = scene_layout(&d, p.NP, grad);
   p.tpw = p.H / 64;
+  p.l = scene_launch_layout(d, p.NP, p.tpw, grad);
   return p;
 }
 }  // namespace
@@ -2158,6 +2228,31 @@ int scene_geometry(const g2k_dims& d, bool grad, bool has_h_in, int32_t* out) {
   out[G2K_GEOM_VARIANT] = scene_variant(d, p.l, grad);
   out[G2K_GEOM_LDS_BYTES] = p.l.total * 4;
   out[G2K_GEOM_PED_MAJOR] = (d.flags & G2K_STEP_PRED_PED_MAJOR) ? 1 : 0;
+  return G2K_OK;
+}
+
+// g2k_step_fixed_geometry (include/g2k_step_fixed.h): host arithmetic only
+int scene_fixed_geometry(const g2k_dims& d, bool grad, bool has_h_in, int32_t* out) {
+  const ScenePlan p = scene_plan(d, grad, has_h_in);
+  const int64_t lds = (int64_t)p.l.total * 4;
+  if (lds > 160 * 1024)
+    return set_err(G2K_ELDS, "Nmax=%d, stride=%d needs %lld bytes of LDS", d.Nmax, d.stride,
+                   (long long)lds);
+  const bool fixed = scene_fixed(d, p.l, p.NP, p.tpw, grad);
+  // workgroups a CU holds: the fixed build as often as its LDS fits, at most
+  // three (24 of the CU's waves at <= 80 VGPRs) — two at H 256, whose build
+  // needs 90 VGPRs (scene_waves_per_eu); the other co-resident forward builds
+  // two (sized for 4 waves per SIMD); every other build one
+  int wgs = 1;
+  if (fixed) {
+    const int cap = p.tpw < kFixedTpw3 ? 3 : 2, fit = (int)(160 * 1024 / lds);
+    wgs = fit < cap ? fit : cap;
+  } else if (!grad && p.NP == 4 && p.tpw < 8) {
+    wgs = 2;
+  }
+  out[G2K_STEP_FIXED_FRAMES] = fixed ? kFixedFrames : 0;
+  out[G2K_STEP_FIXED_WGS_PER_CU] = wgs;
+  out[G2K_STEP_FIXED_LDS_BYTES] = (int32_t)lds;
   return G2K_OK;
 }
 

@@ -152,13 +152,50 @@ CORESIDENT_LDS = 80 * 1024     # g2k_scene.hip kCoresidentLds
 
 
 def step_coresidency(S, F, H, Nmax, W, stride, coresident=False, targets_shared=False) -> int:
-    """Workgroups of one step launch a CU holds at once: 2 under
-    G2K_STEP_CORESIDENT when the 8-wave geometry applies (H < 512 and the
-    scene's LDS fits twice, include/g2k_hip.h), else 1."""
+    """Does the co-resident geometry apply?  2 under G2K_STEP_CORESIDENT when
+    the 8-wave geometry applies (H < 512 and the scene's LDS fits twice,
+    include/g2k_hip.h), else 1.  The workgroups a CU really holds (3 for the
+    fixed-frame build at Nmax 32) are step_workgroups_per_cu's answer."""
     if not coresident or H >= 512:
         return 1
     lds = step_lds_bytes(S, F, H, Nmax, W, stride, True, targets_shared)
     return 2 if lds <= CORESIDENT_LDS else 1
+
+
+# include/g2k_step_fixed.h (added after ABI 11: bound by name)
+FIXED_GEOM_FIELDS = ("frames", "workgroups_per_cu", "lds_bytes")
+FIXED_SYMBOLS = {
+    "g2k_step_fixed_geometry": (ctypes.c_int, [ctypes.POINTER(_lib.G2KDims), ctypes.c_int32,
+                                               ctypes.c_int32, ctypes.c_int32,
+                                               ctypes.POINTER(ctypes.c_int32)]),
+}
+
+
+def step_fixed_geometry(S, F, H, Nmax, stride=1, *, train=False, has_h_in=True, cus=256,
+                        pred_layout="band", targets_shared=False, loss="l2", split=0,
+                        coresident=False) -> dict:
+    """Which build of the scene kernel a launch of these dims takes
+    (g2k_step_fixed_geometry: host arithmetic, no HIP call; the arguments of
+    step_geometry): frames = 20 for the fixed-frame forward build (co-resident
+    geometry, stride 1, F = 20, one workgroup per scene), else 0;
+    workgroups_per_cu, the workgroups of the launch a CU holds at once; and
+    lds_bytes."""
+    lib = _lib.bind(_lib.load(), "step_fixed", FIXED_SYMBOLS)
+    W = (max(F, 1) - 1) * stride + OBS_LEN
+    d = _lib.G2KDims(S, F, OBS_LEN, PRED_LEN, HIDDEN_LEN, H, Nmax, W, stride,
+                     step_flags(pred_layout, targets_shared, loss, split, coresident))
+    out = (ctypes.c_int32 * len(FIXED_GEOM_FIELDS))()
+    _lib.check("g2k_step_fixed_geometry",
+               lib.g2k_step_fixed_geometry(ctypes.byref(d), int(train), int(has_h_in), int(cus), out))
+    return dict(zip(FIXED_GEOM_FIELDS, (int(v) for v in out)))
+
+
+def step_workgroups_per_cu(S, F, H, Nmax, W, stride, coresident=False, targets_shared=False) -> int:
+    """Workgroups of one forward step launch a CU holds at once (step_coresidency's
+    arguments): 3, 2 or 1."""
+    del W   # (implied by F and stride)
+    return step_fixed_geometry(S, F, H, Nmax, stride, coresident=coresident,
+                               targets_shared=targets_shared)["workgroups_per_cu"]
 
 
 def device_cus(device) -> int:
