@@ -16,11 +16,9 @@
 // the float32 restatement reproduces exactly.  The sums m, p, d, y are plain
 // fp32 accumulations.
 //
-// Geometry (kin_geom below): sample_scores_kernel's (g2k_scores.hip).  One
-// workgroup of 256 threads per (scene, chunk of FC frames); a pass takes G =
-// min(256 / K, 32) pairs, lane tid owns (pair tid / K, draw tid % K) and LDS
-// slot tid.  A draw's positions are never kept: the step callback of the draw
-// forms the features from the previous position, velocity and speed.  Of the
+// Geometry and pass scaffold: the drawn-once family's (g2k_drawn.h), but for
+// the draw stage.  A draw's positions are never kept: the step callback of the
+// draw forms the features from the previous position, velocity and speed.  Of the
 // 32 features 22 go to the slot, ft[slot][24] = {s_0..s_10, a_0..a_9, st, 0, 0}
 // (96 B, ds_read_b128 aligned: the scores kernel's xy footprint); l_t is one
 // exact subtraction of two stored speeds.  Per pass, five barriers:
@@ -30,7 +28,7 @@
 //   couples  the lane compares its features with the target's (32 bits in one
 //            word, its terms of m and d), then walks the partners l = k + 1,
 //            ..., k + h (mod K) from LDS, 6 ds_read_b128 each, the circular
-//            half range of g2k_scores.hip: its terms of p
+//            half range (drawn_partners): its terms of p
 //   terms    (the slots are dead) the lane leaves its 12 terms and its word in
 //            its own slot: a val[13][256] next to the slots would put the
 //            mixture head's workgroup above 64 KB
@@ -42,19 +40,14 @@
 //   finish   one lane per pair scales the 16 sums and writes them
 // Scene sums: per-workgroup rows in the caller's workspace (tot [S * C][8]
 // int64, sums [S * C][16] f32, hist [S * C][32 B] int32), then
-// g2k_kin_rows_kernel adds a scene's C rows in chunk order; C == 1 writes the
-// outputs directly.
-#include "g2k_checks.h"
-#include "g2k_common.h"
-#include "g2k_head_draw.h"
-#include "g2k_kin.h"
+// drawn_hist_rows_kernel adds a scene's C rows in chunk order; C == 1 writes
+// the outputs directly.
+#include "g2k_drawn.h"
 
 namespace g2k {
 namespace {
 
-constexpr int kKnThreads = 256;
-constexpr int kKnMaxG = 32;                   // pairs per pass: the LDS budget
-constexpr int kKnPitch = 24;                  // floats per draw in LDS (96 B: ds_read_b128 aligned)
+constexpr int kKnThreads = kDrThreads, kKnMaxG = kDrMaxG, kKnPitch = kDrPitch;
 constexpr int kKnRows = G2K_KIN_ROWS;         // 32 features
 constexpr int kKnGroups = G2K_KIN_GROUPS;
 constexpr int kKnCols = G2K_KIN_COLS;         // per_ped's columns
@@ -66,23 +59,8 @@ constexpr int kKnSums = 16;                   // m, p, d, y per group
 constexpr int kKnItems = kKnRows + kKnSums;   // per pair: the rank counts, then the sums
 constexpr int kKnVtPitch = kKnSums + 1;       // odd: the finishing lanes' reads do not collide
 constexpr int kKnTot = 8;
-constexpr int kKnPasses = 4;                  // passes that a workgroup's frames are sized for
 constexpr int kKnLdsBytes = (kKnThreads * kKnPitch + kKnMaxG * kKnPitch + kKnMaxG * kKnVtPitch +
                              kKnRows * G2K_KIN_BMAX + kKnTot + (kKnThreads / 64) * kKnSums) * 4;
-
-struct KinGeom { int G, FC, C; };
-
-inline KinGeom kin_geom(const g2k_dims& d, int K) {
-  KinGeom g;
-  g.G = kKnThreads / K;
-  if (g.G > kKnMaxG) g.G = kKnMaxG;
-  int fc = (kKnPasses * g.G) / d.Nmax;
-  if (fc > d.F) fc = d.F;
-  if (fc < 1) fc = 1;
-  g.FC = fc;
-  g.C = d.F > 0 ? (d.F + fc - 1) / fc : 1;
-  return g;
-}
 
 // ---- the features' arithmetic: one IEEE operation each, never contracted ----
 __device__ __forceinline__ float kn_sub(float a, float b) {
@@ -170,55 +148,36 @@ __global__ void __launch_bounds__(kKnThreads) sample_kin_kernel(
   __shared__ int lt[kKnTot];
   __shared__ float part[kKnThreads / 64][kKnSums];
   const int tid = threadIdx.x;
-  const int s = blockIdx.x / C, c = blockIdx.x - s * C;
-  const int f0 = c * FC;
-  const int fcn = min(FC, F - f0);                         // frames of this chunk (0 when F == 0)
-  const int nact = clampi(n_active[s], 0, Nmax);
-  const int nf = n_frames ? clampi(n_frames[s], 0, F) : F;
-  const int nfc = clampi(nf - f0, 0, fcn);                 // ... of them below n_frames
-  const uint8_t* mask = ped_mask ? ped_mask + (size_t)s * Nmax : nullptr;
+  const DrawnChunk ch = drawn_chunk(n_active, n_frames, ped_mask, F, Nmax, FC, C);
+  const int s = ch.s, f0 = ch.f0, nact = ch.nact;
+  const uint8_t* mask = ch.mask;
 
   Head::template stage<kKnThreads>(head_params, hlds, tid);
   for (int i = tid; i < kKnRows * B; i += kKnThreads) lh[i] = 0;
   if (tid < kKnTot) lt[tid] = 0;
-  // non-pairs: zeros in per_ped
-  if (per_ped) {
-    for (int idx = tid; idx < fcn * Nmax; idx += kKnThreads) {
-      const int fl = idx / Nmax, n = idx - fl * Nmax;
-      const bool pair = fl < nfc && n < nact && (mask ? mask[n] != 0 : true);
-      if (pair) continue;
-      const size_t sf = (size_t)s * F + f0 + fl;
-      float4* o = reinterpret_cast<float4*>(per_ped) + (sf * Nmax + n) * (kKnCols / 4);
-#pragma unroll
-      for (int q = 0; q < kKnCols / 4; ++q) o[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  }
+  if (per_ped) drawn_zero_per_ped<kKnCols / 4>(ch, per_ped, tid);
   __syncthreads();
   Head head;
   head.bind(hlds);
 
-  const int g = tid / K, k = tid - g * K;                  // this lane's pair of the pass and its draw
-  const int npairs = nfc * nact;
-  const uint32_t lo = seed_lo + (uint32_t)k;               // (seed + k) mod 2^64
-  const uint32_t hi = seed_hi + (lo < seed_lo ? 1u : 0u);
-  // the partners of draw k: the next h draws, circularly
-  const int h = (K - 1) / 2 + ((K & 1) == 0 && k < K / 2 ? 1 : 0);
+  const DrawnLane ln = drawn_lane(tid, K, seed_lo, seed_hi);
+  const int npairs = drawn_npairs(ch);
+  const int g = ln.g, k = ln.k;
+  const int h = drawn_partners(K, k);
   const int binw = (K + 1) / B;                            // ranks per bin
   float acc[kKnSums];
 #pragma unroll
   for (int i = 0; i < kKnSums; ++i) acc[i] = 0.f;
 #pragma nounroll
   for (int base = 0; base < npairs; base += G) {           // uniform trip count
-    const int gp = min(G, npairs - base);                  // pairs of this pass
-    // ---- draw ----
-    const int p = base + g;
-    const bool valid = g < gp;
-    const int fl = valid ? p / nact : 0, n = valid ? p - fl * nact : 0;
-    const bool on = valid && (mask ? mask[n] != 0 : true);
+    // ---- draw: its own, not the family's (below) ----
+    const DrawnItem it = drawn_item(ch, base, G, g);
+    const int gp = it.gp, n = it.n;
+    const bool on = it.on;
     KinFeat x;
     if (on) {
-      const size_t sf = (size_t)s * F + f0 + fl;
-      const int64_t e0 = (int64_t)(sf * kL) * Nmax + n;    // element of step 0
+      const size_t sf = drawn_frame(ch, it.fl);
+      const int64_t e0 = drawn_elem0(ch, sf, n);        // element of step 0
       // the target's features first, by draw 0's lane alone, and out of the
       // registers before the draw: 24 coordinates held across the draw (as
       // load_mu_tg would) put the full-covariance instantiation past 256 VGPRs
@@ -242,7 +201,7 @@ __global__ void __launch_bounds__(kKnThreads) sample_kin_kernel(
           mu[2 * t + 1] = pred[pb + (size_t)(kL + t) * Nmax];
         }
       }
-      head.draw(lo, hi, e0, Nmax, mu, [&](int t, float px, float py) { x.step(t, px, py); });
+      head.draw(ln.lo, ln.hi, e0, Nmax, mu, [&](int t, float px, float py) { x.step(t, px, py); });
       x.store(ft + tid * kKnPitch);
     } else {
 #pragma unroll
@@ -398,64 +357,32 @@ __global__ void __launch_bounds__(kKnThreads) sample_kin_kernel(
   if (tid < kKnTot) tot_rows[(size_t)blockIdx.x * kKnTot + tid] = (int64_t)lt[tid];
 }
 
-// sums[s], hist[s] and tot[s] = the sums over the scene's C chunk rows, in
-// chunk order
-__global__ void __launch_bounds__(256) g2k_kin_rows_kernel(const float* __restrict__ sum_rows,
-                                                           const int32_t* __restrict__ hist_rows,
-                                                           const int64_t* __restrict__ tot_rows, int S,
-                                                           int C, int HB, float* __restrict__ sums,
-                                                           int32_t* __restrict__ hist,
-                                                           int64_t* __restrict__ tot) {
-  const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int per = HB + kKnTot + kKnSums;                   // a scene's outputs: hist, tot, sums
-  if (id >= (int64_t)S * per) return;
-  const int64_t s = id / per;
-  const int i = (int)(id - s * per);
-  if (i < HB) {
-    int32_t v = 0;
-    for (int c = 0; c < C; ++c) v += hist_rows[((size_t)s * C + c) * HB + i];
-    hist[s * HB + i] = v;
-  } else if (i < HB + kKnTot) {
-    int64_t v = 0;
-    for (int c = 0; c < C; ++c) v += tot_rows[((size_t)s * C + c) * kKnTot + (i - HB)];
-    tot[s * kKnTot + (i - HB)] = v;
-  } else {
-    const int j = i - HB - kKnTot;
-    float v = 0.f;
-    for (int c = 0; c < C; ++c) v += sum_rows[((size_t)s * C + c) * kKnSums + j];
-    sums[s * kKnSums + j] = v;
-  }
-}
-
 template <class Head>
 int sample_kin_launch(const g2k_dims* d, const float* pred, const float* targets,
                       const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
                       const float* head_params, uint64_t seed, int K, int B, float* per_ped,
                       float* sums, int32_t* hist, int64_t* tot, void* workspace, hipStream_t st) {
-  const KinGeom g = kin_geom(*d, K);
-  const int64_t wgs = (int64_t)d->S * g.C;
-  if (wgs > 0x7fffffff)
-    return set_err(G2K_EINVAL, "%ssample_kin: %lld workgroups", Head::kPrefix, (long long)wgs);
+  DrawnLaunch L;
+  if (const int rc = drawn_launch(d, drawn_geom(*d, K), seed, Head::kPrefix, "sample_kin", L))
+    return rc;
+  const DrawnGeom& g = L.g;
   const int HB = kKnRows * B;
   // the workgroups' rows: tot [S * C][8] int64, sums [S * C][16] f32, then hist
   // [S * C][32 B] int32
   int64_t* tot_rows = static_cast<int64_t*>(workspace);
-  float* sum_rows = reinterpret_cast<float*>(tot_rows + wgs * kKnTot);
-  int32_t* hist_rows = reinterpret_cast<int32_t*>(sum_rows + wgs * kKnSums);
+  float* sum_rows = reinterpret_cast<float*>(tot_rows + L.wgs * kKnTot);
+  int32_t* hist_rows = reinterpret_cast<int32_t*>(sum_rows + L.wgs * kKnSums);
   const float invK = (float)(1.0 / (double)K);
   const float invKK = (float)(2.0 / ((double)K * (double)(K - 1)));
-  const bool direct = g.C == 1;
-  hipLaunchKernelGGL(sample_kin_kernel<Head>, dim3((unsigned)wgs), dim3(kKnThreads), 0, st, pred,
+  hipLaunchKernelGGL(sample_kin_kernel<Head>, dim3((unsigned)L.wgs), dim3(kKnThreads), 0, st, pred,
                      targets, n_active, n_frames, ped_mask, head_params, d->F, d->Nmax, g.FC, g.C, g.G,
-                     K, B, (uint32_t)seed, (uint32_t)(seed >> 32),
-                     (d->flags & G2K_STEP_TARGETS_SHARED) ? 1 : 0, invK, invKK, per_ped,
-                     direct ? sums : sum_rows, direct ? hist : hist_rows, direct ? tot : tot_rows);
-  int rc = check_launch("sample_kin_kernel");
-  if (rc || direct) return rc;
-  const int64_t ids = (int64_t)d->S * (HB + kKnTot + kKnSums);
-  hipLaunchKernelGGL(g2k_kin_rows_kernel, dim3((unsigned)((ids + 255) / 256)), dim3(256), 0, st,
-                     sum_rows, hist_rows, tot_rows, d->S, g.C, HB, sums, hist, tot);
-  return check_launch("g2k_kin_rows_kernel");
+                     K, B, L.seed_lo, L.seed_hi, L.shared_targets, invK, invKK, per_ped,
+                     L.direct ? sums : sum_rows, L.direct ? hist : hist_rows,
+                     L.direct ? tot : tot_rows);
+  const int rc = check_launch("sample_kin_kernel");
+  if (rc || L.direct) return rc;
+  return drawn_hist_rows<kKnTot, kKnSums>(hist_rows, tot_rows, sum_rows, d->S, g.C, HB, hist, tot,
+                                          sums, st);
 }
 
 inline bool kin_bins_ok(int32_t B) { return B >= 1 && B <= G2K_KIN_BMAX; }
@@ -517,20 +444,13 @@ int64_t g2k_sample_kin_workspace_bytes(const g2k_dims* d, int32_t B) {
   return kin_ws_bytes(d, B);
 }
 
-// the launch geometry (kin_geom: host arithmetic, no HIP call), as the launcher
-// works it out
+// the launch geometry (drawn_geom: host arithmetic, no HIP call), as the
+// launcher works it out
 int g2k_sample_kin_geometry(const g2k_dims* d, int32_t K, int32_t* out) {
   if (const int rc = check_dims(d)) return rc;
   if (const int rc = check_pair_sizes(d)) return rc;
   if (const int rc = check_kin_k(K)) return rc;
-  if (!out) return set_err(G2K_EINVAL, "out is NULL");
-  const KinGeom g = kin_geom(*d, K);
-  out[G2K_KIN_GEOM_G] = g.G;
-  out[G2K_KIN_GEOM_LANES] = K;
-  out[G2K_KIN_GEOM_FC] = g.FC;
-  out[G2K_KIN_GEOM_C] = g.C;
-  out[G2K_KIN_GEOM_LDS_BYTES] = kKnLdsBytes;
-  return G2K_OK;
+  return drawn_write_geom(drawn_geom(*d, K), K, kKnLdsBytes, out);
 }
 
 int g2k_sample_kin_f32(const g2k_dims* d, const float* pred, const float* targets,

@@ -13,10 +13,9 @@
 // argmin is not reproducible in f32).  The draws themselves stay f32 in LDS,
 // as in g2k_scores.hip, and are widened where they are used.
 //
-// Geometry (modes_geom below): the shape of sample_scores_kernel.  One
-// workgroup of 256 threads per (scene, chunk of FC frames); a pass takes G
-// pairs, lane tid owns (pair tid / K, draw tid % K) and LDS slot tid; G =
-// min(256 / K, 64 / M, 32): the M centres of every pair of the pass are in
+// Geometry and pass scaffold: the drawn-once family's (g2k_drawn.h), with a
+// cap of its own on the pairs of a pass, G = min(256 / K, 64 / M, 32)
+// (modes_max_g below): the M centres of every pair of the pass are in
 // LDS as doubles, cen[G * M][24] (12 KB at G M = 64, which with the draws'
 // 24 KB and the mixture head's 19 KB stays below 64 KB: two workgroups per
 // CU), and a lane per pair finishes (32).  Per pass:
@@ -37,42 +36,24 @@
 // Control flow is uniform: there is no convergence test.
 // Scene sums: every finishing lane's eight doubles go to LDS at the end, eight
 // lanes add the 32 rows in lane order; per-workgroup rows [S * C][8] of doubles
-// in the caller's workspace, then g2k_modes_rows_kernel adds a scene's C rows in
+// in the caller's workspace, then drawn_rows8_kernel adds a scene's C rows in
 // chunk order and rounds once; C == 1 rounds and writes out directly.
 #include <math.h>
 
-#include "g2k_checks.h"
-#include "g2k_common.h"
-#include "g2k_head_draw.h"
-#include "g2k_modes.h"
+#include "g2k_drawn.h"
 
 namespace g2k {
 namespace {
 
-constexpr int kMoThreads = 256;
-constexpr int kMoMaxG = 32;                   // pairs per pass: a finishing lane each
+constexpr int kMoThreads = kDrThreads, kMoMaxG = kDrMaxG, kMoPitch = kDrPitch;
 constexpr int kMoMaxGM = 64;                  // centres per pass: the LDS budget
-constexpr int kMoPitch = kL2;                 // floats per draw in LDS
-constexpr int kMoPasses = 4;                  // passes that a workgroup's frames are sized for
 // xy, cen, dmin, stat {A, F}, cnt, asg, iner, sums
 constexpr int kMoLdsBytes = kMoThreads * kMoPitch * 4 + kMoMaxGM * kL2 * 8 + kMoThreads * 8 +
                             kMoMaxGM * 2 * 8 + kMoMaxGM * 4 + kMoThreads + kMoMaxG * 8 +
                             kMoMaxG * 8 * 8;
 
-struct ModesGeom { int G, FC, C; };
-
-inline ModesGeom modes_geom(const g2k_dims& d, int K, int M) {
-  ModesGeom g;
-  g.G = kMoThreads / K;
-  if (g.G > kMoMaxGM / M) g.G = kMoMaxGM / M;
-  if (g.G > kMoMaxG) g.G = kMoMaxG;
-  int fc = (kMoPasses * g.G) / d.Nmax;
-  if (fc > d.F) fc = d.F;
-  if (fc < 1) fc = 1;
-  g.FC = fc;
-  g.C = d.F > 0 ? (d.F + fc - 1) / fc : 1;
-  return g;
-}
+// drawn_geom's cap: the pass's G M centres fit
+inline int modes_max_g(int M) { return kMoMaxGM / M < kMoMaxG ? kMoMaxGM / M : kMoMaxG; }
 
 // the lane's draw against its pair's M centres: the lowest m of the smallest
 // d2 (j ascending), and that d2
@@ -114,25 +95,21 @@ __global__ void __launch_bounds__(kMoThreads) sample_modes_kernel(
   __shared__ double iner[kMoMaxG];
   __shared__ double sums[kMoMaxG][8];
   const int tid = threadIdx.x;
-  const int s = blockIdx.x / C, c = blockIdx.x - s * C;
-  const int f0 = c * FC;
-  const int fcn = min(FC, F - f0);                         // frames of this chunk (0 when F == 0)
-  const int nact = clampi(n_active[s], 0, Nmax);
-  const int nf = n_frames ? clampi(n_frames[s], 0, F) : F;
-  const int nfc = clampi(nf - f0, 0, fcn);                 // ... of them below n_frames
-  const uint8_t* mask = ped_mask ? ped_mask + (size_t)s * Nmax : nullptr;
+  const DrawnChunk ch = drawn_chunk(n_active, n_frames, ped_mask, F, Nmax, FC, C);
+  const int s = ch.s, f0 = ch.f0, fcn = ch.fcn, nact = ch.nact;
+  const uint8_t* mask = ch.mask;
 
   Head::template stage<kMoThreads>(head_params, hlds, tid);
-  // non-pairs: zeros in per_ped, centres and weights
+  // non-pairs: zeros in per_ped, centres and weights (one loop over the three,
+  // so not drawn_zero_per_ped)
   if (per_ped || centres || weights) {
     const int rows_c = centres ? M * kL2 : 0, rows_w = weights ? M : 0, rows_p = per_ped ? 1 : 0;
     const int nrows = rows_c + rows_w + rows_p;
     for (int idx = tid; idx < fcn * nrows * Nmax; idx += kMoThreads) {
       const int n = idx % Nmax;
       const int r = (idx / Nmax) % nrows, fl = idx / (Nmax * nrows);
-      const bool pair = fl < nfc && n < nact && (mask ? mask[n] != 0 : true);
-      if (pair) continue;
-      const size_t sf = (size_t)s * F + f0 + fl;
+      if (drawn_is_pair(ch, fl, n)) continue;
+      const size_t sf = drawn_frame(ch, fl);
       if (r < rows_c) {
         centres[(sf * M * kL2 + r) * Nmax + n] = 0.f;
       } else if (r < rows_c + rows_w) {
@@ -148,39 +125,32 @@ __global__ void __launch_bounds__(kMoThreads) sample_modes_kernel(
   Head head;
   head.bind(hlds);
 
-  const int g = tid / K, k = tid - g * K;                  // this lane's pair of the pass and its draw
-  const int npairs = nfc * nact;
-  const uint32_t lo = seed_lo + (uint32_t)k;               // (seed + k) mod 2^64
-  const uint32_t hi = seed_hi + (lo < seed_lo ? 1u : 0u);
+  const DrawnLane ln = drawn_lane(tid, K, seed_lo, seed_hi);
+  const int npairs = drawn_npairs(ch);
+  const int g = ln.g;
   const double dK = (double)K;                             // w_m = n_m / K, the inertia = sum / K: divided, as defined
   double acc[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) acc[i] = 0.0;
 #pragma nounroll
   for (int base = 0; base < npairs; base += G) {           // uniform trip count
-    const int gp = min(G, npairs - base);                  // pairs of this pass
     // ---- draw ----
-    const int p = base + g;
-    const bool valid = g < gp;
-    const int fl = valid ? p / nact : 0, n = valid ? p - fl * nact : 0;
-    const bool on = valid && (mask ? mask[n] != 0 : true);
+    const DrawnItem it = drawn_item(ch, base, G, g);
+    const int gp = it.gp;
+    const bool valid = it.valid, on = it.on;
     float x[kL2];
     if (on) {
-      const size_t sf = (size_t)s * F + f0 + fl;
-      const int64_t e0 = (int64_t)(sf * kL) * Nmax + n;    // element of step 0
+      const size_t sf = drawn_frame(ch, it.fl);
+      const int64_t e0 = drawn_elem0(ch, sf, it.n);        // element of step 0
       float mu[kL2], tg[kL2];
-      load_mu_tg(true, pred, targets, sf, shared_targets ? (size_t)s : sf, n, Nmax, mu, tg);
-      head.draw(lo, hi, e0, Nmax, mu, [&](int t, float px, float py) {
+      load_mu_tg(true, pred, targets, sf, shared_targets ? (size_t)s : sf, it.n, Nmax, mu, tg);
+      head.draw(ln.lo, ln.hi, e0, Nmax, mu, [&](int t, float px, float py) {
         x[2 * t] = px;
         x[2 * t + 1] = py;
       });
-      float4* o = reinterpret_cast<float4*>(xy + tid * kMoPitch);
-#pragma unroll
-      for (int q = 0; q < kL2 / 4; ++q)
-        o[q] = make_float4(x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]);
+      store_draw(xy + tid * kMoPitch, x);
     } else {
-#pragma unroll
-      for (int i = 0; i < kL2; ++i) x[i] = 0.f;
+      zero_draw(x);
     }
     __syncthreads();
     // ---- start: c_m = X_m ----
@@ -341,38 +311,24 @@ __global__ void __launch_bounds__(kMoThreads) sample_modes_kernel(
   }
 }
 
-// out[s][i] = the sum over the scene's C chunk rows, in chunk order, rounded once
-__global__ void __launch_bounds__(256) g2k_modes_rows_kernel(const double* __restrict__ rows, int S,
-                                                             int C, float* __restrict__ out) {
-  const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (id >= (int64_t)S * 8) return;
-  const int64_t s = id >> 3;
-  const int i = (int)(id & 7);
-  double v = 0.0;
-  for (int c = 0; c < C; ++c) v += rows[((size_t)s * C + c) * 8 + i];
-  out[id] = (float)v;
-}
-
 template <class Head>
 int sample_modes_launch(const g2k_dims* d, const float* pred, const float* targets,
                         const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
                         const float* head_params, uint64_t seed, int K, int M, int iters,
                         float miss_radius, float* per_ped, float* centres, float* weights, float* out,
                         double* rows, hipStream_t st) {
-  const ModesGeom g = modes_geom(*d, K, M);
-  const int64_t wgs = (int64_t)d->S * g.C;
-  if (wgs > 0x7fffffff)
-    return set_err(G2K_EINVAL, "%ssample_modes: %lld workgroups", Head::kPrefix, (long long)wgs);
-  hipLaunchKernelGGL(sample_modes_kernel<Head>, dim3((unsigned)wgs), dim3(kMoThreads), 0, st, pred,
+  DrawnLaunch L;
+  if (const int rc = drawn_launch(d, drawn_geom(*d, K, modes_max_g(M)), seed, Head::kPrefix,
+                                  "sample_modes", L))
+    return rc;
+  const DrawnGeom& g = L.g;
+  hipLaunchKernelGGL(sample_modes_kernel<Head>, dim3((unsigned)L.wgs), dim3(kMoThreads), 0, st, pred,
                      targets, n_active, n_frames, ped_mask, head_params, d->F, d->Nmax, g.FC, g.C, g.G,
-                     K, M, iters, (uint32_t)seed, (uint32_t)(seed >> 32),
-                     (d->flags & G2K_STEP_TARGETS_SHARED) ? 1 : 0, (double)miss_radius, per_ped,
-                     centres, weights, out, g.C == 1 ? (double*)nullptr : rows);
-  int rc = check_launch("sample_modes_kernel");
-  if (rc || g.C == 1) return rc;
-  hipLaunchKernelGGL(g2k_modes_rows_kernel, dim3((unsigned)(((int64_t)d->S * 8 + 255) / 256)),
-                     dim3(256), 0, st, rows, d->S, g.C, out);
-  return check_launch("g2k_modes_rows_kernel");
+                     K, M, iters, L.seed_lo, L.seed_hi, L.shared_targets, (double)miss_radius, per_ped,
+                     centres, weights, out, L.direct ? (double*)nullptr : rows);
+  const int rc = check_launch("sample_modes_kernel");
+  if (rc || L.direct) return rc;
+  return drawn_rows8(rows, d->S, g.C, out, st);
 }
 
 // one row [8] of doubles per (scene, chunk); FC >= 1 frame per chunk, so at most F chunks
@@ -433,20 +389,13 @@ int64_t g2k_sample_modes_workspace_bytes(const g2k_dims* d) {
   return modes_ws_bytes(d);
 }
 
-// the launch geometry (modes_geom: host arithmetic, no HIP call), as the
+// the launch geometry (drawn_geom: host arithmetic, no HIP call), as the
 // launcher works it out
 int g2k_sample_modes_geometry(const g2k_dims* d, int32_t K, int32_t M, int32_t* out) {
   if (const int rc = check_dims(d)) return rc;
   if (const int rc = check_pair_sizes(d)) return rc;
   if (const int rc = modes_params_ok(K, M)) return rc;
-  if (!out) return set_err(G2K_EINVAL, "out is NULL");
-  const ModesGeom g = modes_geom(*d, K, M);
-  out[G2K_MODES_GEOM_G] = g.G;
-  out[G2K_MODES_GEOM_LANES] = K;
-  out[G2K_MODES_GEOM_FC] = g.FC;
-  out[G2K_MODES_GEOM_C] = g.C;
-  out[G2K_MODES_GEOM_LDS_BYTES] = kMoLdsBytes;
-  return G2K_OK;
+  return drawn_write_geom(drawn_geom(*d, K, modes_max_g(M)), K, kMoLdsBytes, out);
 }
 
 int g2k_sample_modes_f32(const g2k_dims* d, const float* pred, const float* targets,

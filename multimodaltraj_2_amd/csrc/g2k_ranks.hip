@@ -26,11 +26,8 @@
 // pairs' ranks in bins floor(r B / (K + 1)); tot [S, 4] int64 = {pairs,
 // degenerate steps, sum r_t, sum r_traj}.  Integers only across pairs.
 //
-// Geometry (ranks_geom below): sample_scores_kernel's (g2k_scores.hip).  One
-// workgroup of 256 threads per (scene, chunk of FC frames); a pass takes G =
-// min(256 / K, 32) pairs, lane tid owns (pair tid / K, draw tid % K) and LDS
-// slot tid, a draw is made ONCE and kept in LDS, xy[slot][24] (time-major, 96
-// B, ds_read_b128 aligned; the pitch of g2k_scores.hip, where 28 floats
+// Geometry and pass scaffold: the drawn-once family's (g2k_drawn.h); the draws
+// in xy[slot][24], time-major (the pitch of g2k_scores.hip, where 28 floats
 // measured the same).  Per pass, six barriers:
 //   draw     the lane draws X_k into registers and its slot; draw 0's lane puts
 //            the pair's target and means next to them
@@ -64,39 +61,20 @@
 // terms against the target costs the fourth barrier and saves [13][256] floats,
 // without which the cap would be 8.
 // Scene sums: per-workgroup integer rows in the caller's workspace (tot
-// [S * C][4] int64, then hist [S * C][13 B] int32), then g2k_ranks_rows_kernel
+// [S * C][4] int64, then hist [S * C][13 B] int32), then drawn_hist_rows_kernel
 // adds a scene's C rows in chunk order; C == 1 writes hist and tot directly.
-#include "g2k_checks.h"
-#include "g2k_common.h"
-#include "g2k_head_draw.h"
-#include "g2k_ranks.h"
+#include "g2k_drawn.h"
 
 namespace g2k {
 namespace {
 
-constexpr int kRkThreads = 256;
-constexpr int kRkMaxG = 32;                   // pairs per pass: the LDS budget
-constexpr int kRkPitch = kL2;                 // floats per draw in LDS (96 B: ds_read_b128 aligned)
+constexpr int kRkThreads = kDrThreads, kRkMaxG = kDrMaxG, kRkPitch = kDrPitch;
 constexpr int kRkRows = G2K_RANKS_ROWS;       // 13: the steps' ranks and the trajectory's
 constexpr int kRkItems = kRkRows + 1;         // the count stage: the rows, then the pair's own item
-constexpr int kRkPasses = 4;                  // passes that a workgroup's frames are sized for
+constexpr int kRkTot = 4;
 constexpr int kRkLdsBytes = (kRkThreads * kRkPitch + 2 * kRkMaxG * kL2 + kRkMaxG * kL * 4 +
                              kRkMaxG * kRkRows + kRkThreads + kRkRows * G2K_RANKS_BMAX + 4) * 4;
 constexpr float kRkFar = -3.0e38f;            // a NaN exponent counts as far away (kde_nll_kernel's)
-
-struct RanksGeom { int G, FC, C; };
-
-inline RanksGeom ranks_geom(const g2k_dims& d, int K) {
-  RanksGeom g;
-  g.G = kRkThreads / K;
-  if (g.G > kRkMaxG) g.G = kRkMaxG;
-  int fc = (kRkPasses * g.G) / d.Nmax;
-  if (fc > d.F) fc = d.F;
-  if (fc < 1) fc = 1;
-  g.FC = fc;
-  g.C = d.F > 0 ? (d.F + fc - 1) / fc : 1;
-  return g;
-}
 
 __device__ __forceinline__ float rk_sqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
 __device__ __forceinline__ float rk_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
@@ -130,73 +108,46 @@ __global__ void __launch_bounds__(kRkThreads, 2) sample_ranks_kernel(
   __shared__ int lh[kRkRows * G2K_RANKS_BMAX];
   __shared__ int lt[4];
   const int tid = threadIdx.x;
-  const int s = blockIdx.x / C, c = blockIdx.x - s * C;
-  const int f0 = c * FC;
-  const int fcn = min(FC, F - f0);                         // frames of this chunk (0 when F == 0)
-  const int nact = clampi(n_active[s], 0, Nmax);
-  const int nf = n_frames ? clampi(n_frames[s], 0, F) : F;
-  const int nfc = clampi(nf - f0, 0, fcn);                 // ... of them below n_frames
-  const uint8_t* mask = ped_mask ? ped_mask + (size_t)s * Nmax : nullptr;
+  const DrawnChunk ch = drawn_chunk(n_active, n_frames, ped_mask, F, Nmax, FC, C);
+  const int s = ch.s, f0 = ch.f0, nact = ch.nact;
+  const uint8_t* mask = ch.mask;
 
   Head::template stage<kRkThreads>(head_params, hlds, tid);
   for (int i = tid; i < kRkRows * B; i += kRkThreads) lh[i] = 0;
   if (tid < 4) lt[tid] = 0;
-  // non-pairs: zeros in per_ped
-  if (per_ped) {
-    for (int idx = tid; idx < fcn * Nmax; idx += kRkThreads) {
-      const int fl = idx / Nmax, n = idx - fl * Nmax;
-      const bool pair = fl < nfc && n < nact && (mask ? mask[n] != 0 : true);
-      if (pair) continue;
-      const size_t sf = (size_t)s * F + f0 + fl;
-      float4* o = reinterpret_cast<float4*>(per_ped) + (sf * Nmax + n) * 4;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) o[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  }
+  if (per_ped) drawn_zero_per_ped<4>(ch, per_ped, tid);               // 16 columns
   __syncthreads();
   Head head;
   head.bind(hlds);
 
-  const int g = tid / K, k = tid - g * K;                  // this lane's pair of the pass and its draw
-  const int npairs = nfc * nact;
-  const uint32_t lo = seed_lo + (uint32_t)k;               // (seed + k) mod 2^64
-  const uint32_t hi = seed_hi + (lo < seed_lo ? 1u : 0u);
+  const DrawnLane ln = drawn_lane(tid, K, seed_lo, seed_hi);
+  const int npairs = drawn_npairs(ch);
+  const int g = ln.g, k = ln.k;
   const int binw = (K + 1) / B;                            // ranks per bin
   const double rK = 1.0 / (double)K, rK1 = 1.0 / (double)(K + 1);
 #pragma nounroll
   for (int base = 0; base < npairs; base += G) {           // uniform trip count
-    const int gp = min(G, npairs - base);                  // pairs of this pass
     // ---- draw ----
-    const int p = base + g;
-    const bool valid = g < gp;
-    const int fl = valid ? p / nact : 0, n = valid ? p - fl * nact : 0;
-    const bool on = valid && (mask ? mask[n] != 0 : true);
+    const DrawnItem it = drawn_item(ch, base, G, g);
+    const int gp = it.gp;
+    const bool on = it.on;
     float x[kL2];
     if (on) {
-      const size_t sf = (size_t)s * F + f0 + fl;
-      const int64_t e0 = (int64_t)(sf * kL) * Nmax + n;    // element of step 0
+      const size_t sf = drawn_frame(ch, it.fl);
+      const int64_t e0 = drawn_elem0(ch, sf, it.n);        // element of step 0
       float mu[kL2], tg[kL2];
-      load_mu_tg(true, pred, targets, sf, shared_targets ? (size_t)s : sf, n, Nmax, mu, tg);
-      head.draw(lo, hi, e0, Nmax, mu, [&](int t, float px, float py) {
+      load_mu_tg(true, pred, targets, sf, shared_targets ? (size_t)s : sf, it.n, Nmax, mu, tg);
+      head.draw(ln.lo, ln.hi, e0, Nmax, mu, [&](int t, float px, float py) {
         x[2 * t] = px;
         x[2 * t + 1] = py;
       });
-      float4* o = reinterpret_cast<float4*>(xy + tid * kRkPitch);
-#pragma unroll
-      for (int q = 0; q < kL2 / 4; ++q)
-        o[q] = make_float4(x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]);
+      store_draw(xy + tid * kRkPitch, x);
       if (k == 0) {
-        float4* ot = reinterpret_cast<float4*>(tgs + g * kL2);
-        float4* om = reinterpret_cast<float4*>(mus + g * kL2);
-#pragma unroll
-        for (int q = 0; q < kL2 / 4; ++q) {
-          ot[q] = make_float4(tg[4 * q], tg[4 * q + 1], tg[4 * q + 2], tg[4 * q + 3]);
-          om[q] = make_float4(mu[4 * q], mu[4 * q + 1], mu[4 * q + 2], mu[4 * q + 3]);
-        }
+        store_draw(tgs + g * kL2, tg);
+        store_draw(mus + g * kL2, mu);
       }
     } else {
-#pragma unroll
-      for (int i = 0; i < kL2; ++i) x[i] = 0.f;
+      zero_draw(x);
     }
     __syncthreads();
     // ---- moments: item (pair, step), the K slots and then the target ----
@@ -371,53 +322,28 @@ __global__ void __launch_bounds__(kRkThreads, 2) sample_ranks_kernel(
   if (tid < 4) tot_rows[(size_t)blockIdx.x * 4 + tid] = (int64_t)lt[tid];
 }
 
-// hist[s] and tot[s] = the sums over the scene's C chunk rows, in chunk order
-__global__ void __launch_bounds__(256) g2k_ranks_rows_kernel(const int32_t* __restrict__ hist_rows,
-                                                             const int64_t* __restrict__ tot_rows,
-                                                             int S, int C, int HB,
-                                                             int32_t* __restrict__ hist,
-                                                             int64_t* __restrict__ tot) {
-  const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int per = HB + 4;                                  // a scene's outputs: hist [13 B], tot [4]
-  if (id >= (int64_t)S * per) return;
-  const int64_t s = id / per;
-  const int i = (int)(id - s * per);
-  if (i < HB) {
-    int32_t v = 0;
-    for (int c = 0; c < C; ++c) v += hist_rows[((size_t)s * C + c) * HB + i];
-    hist[s * HB + i] = v;
-  } else {
-    int64_t v = 0;
-    for (int c = 0; c < C; ++c) v += tot_rows[((size_t)s * C + c) * 4 + (i - HB)];
-    tot[s * 4 + (i - HB)] = v;
-  }
-}
-
 template <class Head>
 int sample_ranks_launch(const g2k_dims* d, const float* pred, const float* targets,
                         const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
                         const float* head_params, uint64_t seed, int K, int B, float* per_ped,
                         int32_t* hist, int64_t* tot, void* workspace, hipStream_t st) {
-  const RanksGeom g = ranks_geom(*d, K);
-  const int64_t wgs = (int64_t)d->S * g.C;
-  if (wgs > 0x7fffffff)
-    return set_err(G2K_EINVAL, "%ssample_ranks: %lld workgroups", Head::kPrefix, (long long)wgs);
+  DrawnLaunch L;
+  if (const int rc = drawn_launch(d, drawn_geom(*d, K), seed, Head::kPrefix, "sample_ranks", L))
+    return rc;
+  const DrawnGeom& g = L.g;
   const int HB = kRkRows * B;
   // the workgroups' rows: tot [S * C][4] int64, then hist [S * C][13 B] int32
   int64_t* tot_rows = static_cast<int64_t*>(workspace);
-  int32_t* hist_rows = reinterpret_cast<int32_t*>(tot_rows + wgs * 4);
+  int32_t* hist_rows = reinterpret_cast<int32_t*>(tot_rows + L.wgs * kRkTot);
   const double scott = pow((double)(K + 1), -1.0 / 3.0);
-  hipLaunchKernelGGL(sample_ranks_kernel<Head>, dim3((unsigned)wgs), dim3(kRkThreads), 0, st, pred,
+  hipLaunchKernelGGL(sample_ranks_kernel<Head>, dim3((unsigned)L.wgs), dim3(kRkThreads), 0, st, pred,
                      targets, n_active, n_frames, ped_mask, head_params, d->F, d->Nmax, g.FC, g.C, g.G,
-                     K, B, (uint32_t)seed, (uint32_t)(seed >> 32),
-                     (d->flags & G2K_STEP_TARGETS_SHARED) ? 1 : 0, scott, per_ped,
-                     g.C == 1 ? hist : hist_rows, g.C == 1 ? tot : tot_rows);
-  int rc = check_launch("sample_ranks_kernel");
-  if (rc || g.C == 1) return rc;
-  const int64_t ids = (int64_t)d->S * (HB + 4);
-  hipLaunchKernelGGL(g2k_ranks_rows_kernel, dim3((unsigned)((ids + 255) / 256)), dim3(256), 0, st,
-                     hist_rows, tot_rows, d->S, g.C, HB, hist, tot);
-  return check_launch("g2k_ranks_rows_kernel");
+                     K, B, L.seed_lo, L.seed_hi, L.shared_targets, scott, per_ped,
+                     L.direct ? hist : hist_rows, L.direct ? tot : tot_rows);
+  const int rc = check_launch("sample_ranks_kernel");
+  if (rc || L.direct) return rc;
+  return drawn_hist_rows<kRkTot, 0>(hist_rows, tot_rows, nullptr, d->S, g.C, HB, hist, tot, nullptr,
+                                    st);
 }
 
 inline bool ranks_bins_ok(int32_t B) { return B >= 1 && B <= G2K_RANKS_BMAX; }
@@ -479,20 +405,13 @@ int64_t g2k_sample_ranks_workspace_bytes(const g2k_dims* d, int32_t B) {
   return ranks_ws_bytes(d, B);
 }
 
-// the launch geometry (ranks_geom: host arithmetic, no HIP call), as the
+// the launch geometry (drawn_geom: host arithmetic, no HIP call), as the
 // launcher works it out
 int g2k_sample_ranks_geometry(const g2k_dims* d, int32_t K, int32_t* out) {
   if (const int rc = check_dims(d)) return rc;
   if (const int rc = check_pair_sizes(d)) return rc;
   if (const int rc = check_ranks_k(K)) return rc;
-  if (!out) return set_err(G2K_EINVAL, "out is NULL");
-  const RanksGeom g = ranks_geom(*d, K);
-  out[G2K_RANKS_GEOM_G] = g.G;
-  out[G2K_RANKS_GEOM_LANES] = K;
-  out[G2K_RANKS_GEOM_FC] = g.FC;
-  out[G2K_RANKS_GEOM_C] = g.C;
-  out[G2K_RANKS_GEOM_LDS_BYTES] = kRkLdsBytes;
-  return G2K_OK;
+  return drawn_write_geom(drawn_geom(*d, K), K, kRkLdsBytes, out);
 }
 
 int g2k_sample_ranks_f32(const g2k_dims* d, const float* pred, const float* targets,

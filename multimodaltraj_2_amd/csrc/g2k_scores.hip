@@ -26,22 +26,17 @@
 // atomics.  The host forms es_traj = mR - pR / 2 (the fair energy score of the
 // 24-D law), es_ade = mA - pA / 2, es_fde = mF - pF / 2.
 //
-// Geometry (scores_geom below).  Unlike best-of-K and the KDE-NLL, the K draws
-// of a pair must all be live at once: every couple of them is compared.  A
-// draw is made ONCE and kept in LDS, xy[slot][24] (time-major, 96 B; a pitch of
-// 28 floats, which spreads the 16 lanes of a ds_read_b128 group over 16
-// different bank quads where 24 collides two ways, measured the same to within
-// 1 %: DESIGN.md §6j — the walk is not bound by LDS reads).  One
-// workgroup of 256 threads per (scene, chunk of FC frames); a pass takes G =
-// min(256 / K, 32) pairs, lane tid owns (pair tid / K, draw tid % K) and LDS
-// slot tid.  Per pass, three barriers:
+// Geometry and pass scaffold: the drawn-once family's (g2k_drawn.h) — every
+// couple of a pair's K draws is compared, so the draws are all live at once,
+// xy[slot][24] (time-major; a pitch of 28 floats, which spreads the 16 lanes
+// of a ds_read_b128 group over 16 different bank quads where 24 collides two
+// ways, measured the same to within 1 %: DESIGN.md §6j — the walk is not bound
+// by LDS reads).  Per pass, three barriers:
 //   draw     the lane draws X_k into registers, takes a, f, r against the
 //            target and stores X_k in its slot
 //   couples  the lane walks the partners l = k + 1, ..., k + h (mod K) from
-//            LDS, 6 ds_read_b128 each, h = (K - 1) / 2, one more for the lanes
-//            k < K / 2 of an even K (the antipodal couple once): a circular
-//            half range counts every unordered couple once.  The lane's six
-//            sums go to val[6][256]
+//            LDS, 6 ds_read_b128 each, the circular half range
+//            (drawn_partners).  The lane's six sums go to val[6][256]
 //   items    72 items per pair dealt to the 256 lanes: 66 step pairs (t, u),
 //            each a walk over the K slots (2 ds_read_b64 and two square roots
 //            per draw) and the squared difference from the target's variogram;
@@ -53,38 +48,18 @@
 // lanes idle only below K = 8.  Square roots: sqrtf against the target (as
 // g2k_bestk.hip), v_sqrt_f32 (1 ulp) among the draws and in the variogram.
 // Scene sums: per-workgroup rows [S * C][8] in the caller's workspace, then
-// g2k_scores_rows_kernel adds a scene's C rows in chunk order; C == 1 writes
-// out directly.
-#include "g2k_checks.h"
-#include "g2k_common.h"
-#include "g2k_head_draw.h"
-#include "g2k_scores.h"
+// drawn_rows8_kernel adds a scene's C rows in chunk order; C == 1 writes out
+// directly.
+#include "g2k_drawn.h"
 
 namespace g2k {
 namespace {
 
-constexpr int kScThreads = 256;
-constexpr int kScMaxG = 32;                   // pairs per pass: the LDS budget
-constexpr int kScPitch = kL2;                 // floats per draw in LDS (96 B: ds_read_b128 aligned)
+constexpr int kScThreads = kDrThreads, kScMaxG = kDrMaxG, kScPitch = kDrPitch;
 constexpr int kScStepPairs = kL * (kL - 1) / 2;   // 66
 constexpr int kScItems = kScStepPairs + 6;    // per pair: the step pairs, then the six column sums
 constexpr int kScVtPitch = kScItems + 1;      // odd: the finishing lanes' reads do not collide
-constexpr int kScPasses = 4;                  // passes that a workgroup's frames are sized for
 constexpr int kScLdsBytes = (kScThreads * kScPitch + 6 * kScThreads + kScMaxG * kScVtPitch + 4 * 8) * 4;
-
-struct ScoresGeom { int G, FC, C; };
-
-inline ScoresGeom scores_geom(const g2k_dims& d, int K) {
-  ScoresGeom g;
-  g.G = kScThreads / K;
-  if (g.G > kScMaxG) g.G = kScMaxG;
-  int fc = (kScPasses * g.G) / d.Nmax;
-  if (fc > d.F) fc = d.F;
-  if (fc < 1) fc = 1;
-  g.FC = fc;
-  g.C = d.F > 0 ? (d.F + fc - 1) / fc : 1;
-  return g;
-}
 
 __device__ __forceinline__ float sqrt_ulp(float x) { return __builtin_amdgcn_sqrtf(x); }
 
@@ -101,56 +76,37 @@ __global__ void __launch_bounds__(kScThreads) sample_scores_kernel(
   __shared__ float vt[kScMaxG * kScVtPitch];
   __shared__ float part[kScThreads / 64][8];
   const int tid = threadIdx.x;
-  const int s = blockIdx.x / C, c = blockIdx.x - s * C;
-  const int f0 = c * FC;
-  const int fcn = min(FC, F - f0);                         // frames of this chunk (0 when F == 0)
-  const int nact = clampi(n_active[s], 0, Nmax);
-  const int nf = n_frames ? clampi(n_frames[s], 0, F) : F;
-  const int nfc = clampi(nf - f0, 0, fcn);                 // ... of them below n_frames
-  const uint8_t* mask = ped_mask ? ped_mask + (size_t)s * Nmax : nullptr;
+  const DrawnChunk ch = drawn_chunk(n_active, n_frames, ped_mask, F, Nmax, FC, C);
+  const int s = ch.s, f0 = ch.f0, nact = ch.nact;
+  const uint8_t* mask = ch.mask;
 
   Head::template stage<kScThreads>(head_params, hlds, tid);
-  // non-pairs: zeros in per_ped
-  if (per_ped) {
-    for (int idx = tid; idx < fcn * Nmax; idx += kScThreads) {
-      const int fl = idx / Nmax, n = idx - fl * Nmax;
-      const bool pair = fl < nfc && n < nact && (mask ? mask[n] != 0 : true);
-      if (pair) continue;
-      const size_t sf = (size_t)s * F + f0 + fl;
-      float4* o = reinterpret_cast<float4*>(per_ped) + (sf * Nmax + n) * 2;
-      o[0] = make_float4(0.f, 0.f, 0.f, 0.f);
-      o[1] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  }
+  if (per_ped) drawn_zero_per_ped<2>(ch, per_ped, tid);
   __syncthreads();
   Head head;
   head.bind(hlds);
 
-  const int g = tid / K, k = tid - g * K;                  // this lane's pair of the pass and its draw
-  const int npairs = nfc * nact;
-  const uint32_t lo = seed_lo + (uint32_t)k;               // (seed + k) mod 2^64
-  const uint32_t hi = seed_hi + (lo < seed_lo ? 1u : 0u);
-  // the partners of draw k: the next h draws, circularly
-  const int h = (K - 1) / 2 + ((K & 1) == 0 && k < K / 2 ? 1 : 0);
+  const DrawnLane ln = drawn_lane(tid, K, seed_lo, seed_hi);
+  const int npairs = drawn_npairs(ch);
+  const int g = ln.g, k = ln.k;
+  const int h = drawn_partners(K, k);
   float acc[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) acc[i] = 0.f;
 #pragma nounroll
   for (int base = 0; base < npairs; base += G) {           // uniform trip count
-    const int gp = min(G, npairs - base);                  // pairs of this pass
     // ---- draw ----
-    const int p = base + g;
-    const bool valid = g < gp;
-    const int fl = valid ? p / nact : 0, n = valid ? p - fl * nact : 0;
-    const bool on = valid && (mask ? mask[n] != 0 : true);
+    const DrawnItem it = drawn_item(ch, base, G, g);
+    const int gp = it.gp;
+    const bool on = it.on;
     float x[kL2];
     float ta = 0.f, tf = 0.f, tr = 0.f;
     if (on) {
-      const size_t sf = (size_t)s * F + f0 + fl;
-      const int64_t e0 = (int64_t)(sf * kL) * Nmax + n;    // element of step 0
+      const size_t sf = drawn_frame(ch, it.fl);
+      const int64_t e0 = drawn_elem0(ch, sf, it.n);        // element of step 0
       float mu[kL2], tg[kL2];
-      load_mu_tg(true, pred, targets, sf, shared_targets ? (size_t)s : sf, n, Nmax, mu, tg);
-      head.draw(lo, hi, e0, Nmax, mu, [&](int t, float px, float py) {
+      load_mu_tg(true, pred, targets, sf, shared_targets ? (size_t)s : sf, it.n, Nmax, mu, tg);
+      head.draw(ln.lo, ln.hi, e0, Nmax, mu, [&](int t, float px, float py) {
         x[2 * t] = px;
         x[2 * t + 1] = py;
         const float dx = px - tg[2 * t], dy = py - tg[2 * t + 1];
@@ -160,13 +116,9 @@ __global__ void __launch_bounds__(kScThreads) sample_scores_kernel(
         tr += d2;
       });
       tr = sqrtf(tr);
-      float4* o = reinterpret_cast<float4*>(xy + tid * kScPitch);
-#pragma unroll
-      for (int q = 0; q < kL2 / 4; ++q)
-        o[q] = make_float4(x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]);
+      store_draw(xy + tid * kScPitch, x);
     } else {
-#pragma unroll
-      for (int i = 0; i < kL2; ++i) x[i] = 0.f;
+      zero_draw(x);
     }
     __syncthreads();
     // ---- couples ----
@@ -269,44 +221,35 @@ __global__ void __launch_bounds__(kScThreads) sample_scores_kernel(
     rows[(size_t)blockIdx.x * 8 + tid] = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
 }
 
-// out[s][i] = sum over the scene's C chunk rows, in chunk order
-__global__ void __launch_bounds__(256) g2k_scores_rows_kernel(const float* __restrict__ rows, int S,
-                                                              int C, float* __restrict__ out) {
-  const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (id >= (int64_t)S * 8) return;
-  const int64_t s = id >> 3;
-  const int i = (int)(id & 7);
-  float v = 0.f;
-  for (int c = 0; c < C; ++c) v += rows[((size_t)s * C + c) * 8 + i];
-  out[id] = v;
-}
-
 template <class Head>
 int sample_scores_launch(const g2k_dims* d, const float* pred, const float* targets,
                          const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
                          const float* head_params, uint64_t seed, int K, float* per_ped, float* out,
                          float* rows, hipStream_t st) {
-  const ScoresGeom g = scores_geom(*d, K);
-  const int64_t wgs = (int64_t)d->S * g.C;
-  if (wgs > 0x7fffffff)
-    return set_err(G2K_EINVAL, "%ssample_scores: %lld workgroups", Head::kPrefix, (long long)wgs);
+  DrawnLaunch L;
+  if (const int rc = drawn_launch(d, drawn_geom(*d, K), seed, Head::kPrefix, "sample_scores", L))
+    return rc;
+  const DrawnGeom& g = L.g;
   const float invK = (float)(1.0 / (double)K);
   const float invKK = (float)(2.0 / ((double)K * (double)(K - 1)));
-  hipLaunchKernelGGL(sample_scores_kernel<Head>, dim3((unsigned)wgs), dim3(kScThreads), 0, st, pred,
+  hipLaunchKernelGGL(sample_scores_kernel<Head>, dim3((unsigned)L.wgs), dim3(kScThreads), 0, st, pred,
                      targets, n_active, n_frames, ped_mask, head_params, d->F, d->Nmax, g.FC, g.C, g.G,
-                     K, (uint32_t)seed, (uint32_t)(seed >> 32),
-                     (d->flags & G2K_STEP_TARGETS_SHARED) ? 1 : 0, invK, invKK, per_ped,
-                     g.C == 1 ? out : rows);
-  int rc = check_launch("sample_scores_kernel");
-  if (rc || g.C == 1) return rc;
-  hipLaunchKernelGGL(g2k_scores_rows_kernel, dim3((unsigned)(((int64_t)d->S * 8 + 255) / 256)),
-                     dim3(256), 0, st, rows, d->S, g.C, out);
-  return check_launch("g2k_scores_rows_kernel");
+                     K, L.seed_lo, L.seed_hi, L.shared_targets, invK, invKK, per_ped,
+                     L.direct ? out : rows);
+  const int rc = check_launch("sample_scores_kernel");
+  if (rc || L.direct) return rc;
+  return drawn_rows8(rows, d->S, g.C, out, st);
 }
 
 // one row [8] per (scene, chunk); FC >= 1 frame per chunk, so at most F chunks
 int64_t scores_ws_bytes(const g2k_dims* d) {
   return (int64_t)d->S * (d->F > 1 ? d->F : 1) * 8 * 4;
+}
+
+int check_scores_k(int32_t K) {
+  if (K < G2K_SCORES_KMIN || K > G2K_SCORES_KMAX)
+    return set_err(G2K_EINVAL, "K=%d (%d..%d)", K, G2K_SCORES_KMIN, G2K_SCORES_KMAX);
+  return G2K_OK;
 }
 
 // the argument checks, before any HIP call; G2K_OK with S > 0: launch
@@ -317,8 +260,7 @@ int scores_validate(const char* name, const g2k_dims* d, const void* pred, const
   if (d->flags & ~G2K_STEP_TARGETS_SHARED)
     return set_err(G2K_EUNSUPPORTED, "%s: flags %d (0 or G2K_STEP_TARGETS_SHARED)", name, d->flags);
   if (const int rc = check_pair_sizes(d)) return rc;
-  if (K < G2K_SCORES_KMIN || K > G2K_SCORES_KMAX)
-    return set_err(G2K_EINVAL, "K=%d (%d..%d)", K, G2K_SCORES_KMIN, G2K_SCORES_KMAX);
+  if (const int rc = check_scores_k(K)) return rc;
   if (const int rc = check_required({pred, targets, n_active, head, out})) return rc;
   if (const int rc = check_targets(targets)) return rc;
   if (const int rc = check_per_ped(per_ped)) return rc;
@@ -349,21 +291,13 @@ int64_t g2k_sample_scores_workspace_bytes(const g2k_dims* d) {
   return scores_ws_bytes(d);
 }
 
-// the launch geometry (scores_geom: host arithmetic, no HIP call), as the
+// the launch geometry (drawn_geom: host arithmetic, no HIP call), as the
 // launcher works it out
 int g2k_sample_scores_geometry(const g2k_dims* d, int32_t K, int32_t* out) {
   if (const int rc = check_dims(d)) return rc;
   if (const int rc = check_pair_sizes(d)) return rc;
-  if (K < G2K_SCORES_KMIN || K > G2K_SCORES_KMAX)
-    return set_err(G2K_EINVAL, "K=%d (%d..%d)", K, G2K_SCORES_KMIN, G2K_SCORES_KMAX);
-  if (!out) return set_err(G2K_EINVAL, "out is NULL");
-  const ScoresGeom g = scores_geom(*d, K);
-  out[G2K_SCORES_GEOM_G] = g.G;
-  out[G2K_SCORES_GEOM_LANES] = K;
-  out[G2K_SCORES_GEOM_FC] = g.FC;
-  out[G2K_SCORES_GEOM_C] = g.C;
-  out[G2K_SCORES_GEOM_LDS_BYTES] = kScLdsBytes;
-  return G2K_OK;
+  if (const int rc = check_scores_k(K)) return rc;
+  return drawn_write_geom(drawn_geom(*d, K), K, kScLdsBytes, out);
 }
 
 int g2k_sample_scores_f32(const g2k_dims* d, const float* pred, const float* targets,

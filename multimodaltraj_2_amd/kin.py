@@ -22,7 +22,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .frame_step import OBS_LEN, PRED_LEN, _ptr, _stream
+from .frame_step import _ptr, _stream
+from .nll import DRAWN_GEOM_FIELDS, _drawn_geometry
 from .ranks import _dev
 
 KMIN, KMAX, BMAX, ROWS = 2, 255, 64, 32
@@ -31,7 +32,7 @@ AUTO_BINS_MAX = 32
 # group -> the rows of hist (and the columns of per_ped) that hold its ranks
 GROUPS = {"speed": slice(0, 11), "acc": slice(11, 21), "lacc": slice(21, 31), "straight": slice(31, 32)}
 GROUP_NAMES = tuple(GROUPS)
-GEOM_FIELDS = ("g", "lanes", "fc", "c", "lds_bytes")
+GEOM_FIELDS = DRAWN_GEOM_FIELDS
 
 _D = ctypes.POINTER(_lib.G2KDims)
 _vp, _i64, _int, _i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int32
@@ -128,14 +129,9 @@ class SampleKin:
 
 def sample_kin_geometry(S, F, Nmax, k) -> dict:
     """The launch geometry of ``sample_kin`` for these shapes
-    (g2k_sample_kin_geometry: host arithmetic, no HIP call): g pairs per pass of
-    a workgroup, lanes per pair, fc frames per workgroup, c workgroups per scene
-    and the workgroup's LDS bytes without the head's own."""
-    lib = load()
-    d = _lib.G2KDims(S, F, OBS_LEN, PRED_LEN, 16, 64, Nmax, OBS_LEN, 0)
-    out = (_i32 * len(GEOM_FIELDS))()
-    _lib.check("g2k_sample_kin_geometry", lib.g2k_sample_kin_geometry(ctypes.byref(d), int(k), out))
-    return dict(zip(GEOM_FIELDS, (int(v) for v in out)))
+    (g2k_sample_kin_geometry: host arithmetic, no HIP call;
+    the fields of nll._drawn_geometry)."""
+    return _drawn_geometry(load(), "g2k_sample_kin_geometry", S, F, Nmax, k)
 
 
 def check_k_bins(k, bins):

@@ -21,11 +21,11 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from .frame_step import OBS_LEN, PRED_LEN
-from .nll import _launch
+from .frame_step import PRED_LEN
+from .nll import DRAWN_GEOM_FIELDS, _drawn_geometry, _launch
 
 MMAX, KMAX, ITERS_MAX = 32, 256, 64
-GEOM_FIELDS = ("g", "lanes", "fc", "c", "lds_bytes")
+GEOM_FIELDS = DRAWN_GEOM_FIELDS
 
 _D = ctypes.POINTER(_lib.G2KDims)
 _vp, _i64, _int, _i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int32
@@ -111,15 +111,9 @@ class SampleModes:
 
 def sample_modes_geometry(S, F, Nmax, k, modes) -> dict:
     """The launch geometry of ``sample_modes`` for these shapes
-    (g2k_sample_modes_geometry: host arithmetic, no HIP call): g pairs per pass
-    of a workgroup, lanes per pair, fc frames per workgroup, c workgroups per
-    scene and the workgroup's LDS bytes without the head's own."""
-    lib = load()
-    d = _lib.G2KDims(S, F, OBS_LEN, PRED_LEN, 16, 64, Nmax, OBS_LEN, 0)
-    out = (ctypes.c_int32 * len(GEOM_FIELDS))()
-    _lib.check("g2k_sample_modes_geometry",
-               lib.g2k_sample_modes_geometry(ctypes.byref(d), int(k), int(modes), out))
-    return dict(zip(GEOM_FIELDS, (int(v) for v in out)))
+    (g2k_sample_modes_geometry: host arithmetic, no HIP call;
+    the fields of nll._drawn_geometry)."""
+    return _drawn_geometry(load(), "g2k_sample_modes_geometry", S, F, Nmax, k, modes)
 
 
 def _sample_modes(symbol, head, d, pred, targets, n_active, k, modes, iters, seed, miss_radius,

@@ -291,6 +291,24 @@ def best_of_k_geometry(S, F, Nmax, k) -> dict:
     return dict(zip(_lib.BESTK_GEOM_FIELDS, (int(v) for v in out)))
 
 
+# the out[] of the drawn-once evaluations' geometry entry points
+# (G2K_{SCORES,MODES,RANKS,KIN}_GEOM_*: csrc/g2k_drawn.h holds them equal)
+DRAWN_GEOM_FIELDS = ("g", "lanes", "fc", "c", "lds_bytes")
+
+
+def _drawn_geometry(lib, symbol, S, F, Nmax, *params) -> dict:
+    """The launch geometry of a drawn-once sampled evaluation (sample_scores,
+    sample_modes, sample_ranks, sample_kin) for these shapes, from its entry
+    point ``symbol`` on the handle ``lib`` (host arithmetic, no HIP call):
+    g pairs per pass of a workgroup, lanes per pair, fc frames per workgroup,
+    c workgroups per scene and the workgroup's LDS bytes without the head's
+    own.  ``params``: K, and what else the entry point takes before out."""
+    d = _lib.G2KDims(S, F, OBS_LEN, PRED_LEN, 16, 64, Nmax, OBS_LEN, 0)
+    out = (ctypes.c_int32 * len(DRAWN_GEOM_FIELDS))()
+    _lib.check(symbol, getattr(lib, symbol)(ctypes.byref(d), *(int(v) for v in params), out))
+    return dict(zip(DRAWN_GEOM_FIELDS, (int(v) for v in out)))
+
+
 def _launch(lib, symbol, d, pred, targets, n_active, n_frames, ped_mask, head, seed, stream, *args,
             size=None):
     """The tail of every sampled evaluation: the workspace (``size``, the

@@ -22,11 +22,12 @@ import numpy as np
 import torch
 
 from . import _lib
-from .frame_step import OBS_LEN, PRED_LEN, _ptr, _stream
+from .frame_step import PRED_LEN, _ptr, _stream
+from .nll import DRAWN_GEOM_FIELDS, _drawn_geometry
 
 KMIN, KMAX, BMAX, ROWS = 4, 255, 64, 13
 AUTO_BINS_MAX = 32
-GEOM_FIELDS = ("g", "lanes", "fc", "c", "lds_bytes")
+GEOM_FIELDS = DRAWN_GEOM_FIELDS
 
 _D = ctypes.POINTER(_lib.G2KDims)
 _vp, _i64, _int, _i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int32
@@ -146,14 +147,9 @@ class SampleRanks:
 
 def sample_ranks_geometry(S, F, Nmax, k) -> dict:
     """The launch geometry of ``sample_ranks`` for these shapes
-    (g2k_sample_ranks_geometry: host arithmetic, no HIP call): g pairs per
-    pass of a workgroup, lanes per pair, fc frames per workgroup, c workgroups
-    per scene and the workgroup's LDS bytes without the head's own."""
-    lib = load()
-    d = _lib.G2KDims(S, F, OBS_LEN, PRED_LEN, 16, 64, Nmax, OBS_LEN, 0)
-    out = (_i32 * len(GEOM_FIELDS))()
-    _lib.check("g2k_sample_ranks_geometry", lib.g2k_sample_ranks_geometry(ctypes.byref(d), int(k), out))
-    return dict(zip(GEOM_FIELDS, (int(v) for v in out)))
+    (g2k_sample_ranks_geometry: host arithmetic, no HIP call;
+    the fields of nll._drawn_geometry)."""
+    return _drawn_geometry(load(), "g2k_sample_ranks_geometry", S, F, Nmax, k)
 
 
 def check_k_bins(k, bins):
