@@ -5,8 +5,8 @@ the build's own: --data_root (Q8), --device, --mode,
 --sample_seed, --head_log_sigma, --collision_radius, --fit_head,
 --calibration, --fullcov_head, --mixture_head, --mixture_components,
 --mixture_iters, --kde_nll, --kde_floor, --sample_scores, --sample_ranks,
---rank_bins, --sample_kinematics, --kin_bins, --sample_modes, --modes_draws,
---modes_iters, --miss_radius."""
+--rank_bins, --sample_kinematics, --kin_bins, --couple_scores, --couple_bins,
+--couple_reach, --sample_modes, --modes_draws, --modes_iters, --miss_radius."""
 import argparse
 
 
@@ -126,6 +126,20 @@ class ArgsParser:
     parser.add_argument('--kin_bins', type=int, default=0,
                         help='--sample_kinematics: bins of the PIT histograms, a divisor of K + 1 up to '
                              '64 (0: the largest divisor <= 32)')
+    parser.add_argument('--couple_scores', type=int, choices=(0, 1), default=0,
+                        help='--num_samples K (2 <= K <= 64): 1 also reports the couple-distance scores '
+                             'of the K draws taken as joint samples (per couple of pedestrians of a '
+                             'scene, the closest approach and the final separation: the fair CRPS, the '
+                             "targets' mean PIT rank among the draws, the PIT histogram's distance from "
+                             "uniform, the draws' and the targets' mean), of the per-step head and, "
+                             'with --fullcov_head / --mixture_head, of those heads')
+    parser.add_argument('--couple_bins', type=int, default=0,
+                        help='--couple_scores: bins of the PIT histograms, a divisor of K + 1 up to 64 '
+                             '(0: the largest divisor <= 32)')
+    parser.add_argument('--couple_reach', type=float, default=0.0,
+                        help="--couple_scores: score the couples whose mean predictions come closer "
+                             "than this, in the dataset's own units as --collision_radius (0: every "
+                             'couple)')
     parser.add_argument('--sample_modes', type=int, default=0,
                         help='--num_samples: M in 1..32 also reduces --modes_draws draws of each head '
                              'in use to M representative trajectories with probabilities (k-means '

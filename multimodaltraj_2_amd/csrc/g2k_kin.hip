@@ -362,6 +362,14 @@ int sample_kin_launch(const g2k_dims* d, const float* pred, const float* targets
                       const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
                       const float* head_params, uint64_t seed, int K, int B, float* per_ped,
                       float* sums, int32_t* hist, int64_t* tot, void* workspace, hipStream_t st) {
+  if (d->F == 0) {
+    // no frame: no kernel (its staging would read the head's parameters), zeros
+    if (hipMemsetAsync(sums, 0, (size_t)d->S * kKnSums * 4, st) != hipSuccess ||
+        hipMemsetAsync(hist, 0, (size_t)d->S * kKnRows * B * 4, st) != hipSuccess ||
+        hipMemsetAsync(tot, 0, (size_t)d->S * kKnTot * 8, st) != hipSuccess)
+      return set_err(G2K_ELAUNCH, "%ssample_kin: zeroing the outputs failed", Head::kPrefix);
+    return G2K_OK;
+  }
   DrawnLaunch L;
   if (const int rc = drawn_launch(d, drawn_geom(*d, K), seed, Head::kPrefix, "sample_kin", L))
     return rc;

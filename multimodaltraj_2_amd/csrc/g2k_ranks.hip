@@ -327,6 +327,13 @@ int sample_ranks_launch(const g2k_dims* d, const float* pred, const float* targe
                         const int32_t* n_active, const int32_t* n_frames, const uint8_t* ped_mask,
                         const float* head_params, uint64_t seed, int K, int B, float* per_ped,
                         int32_t* hist, int64_t* tot, void* workspace, hipStream_t st) {
+  if (d->F == 0) {
+    // no frame: no kernel (its staging would read the head's parameters), zeros
+    if (hipMemsetAsync(hist, 0, (size_t)d->S * kRkRows * B * 4, st) != hipSuccess ||
+        hipMemsetAsync(tot, 0, (size_t)d->S * kRkTot * 8, st) != hipSuccess)
+      return set_err(G2K_ELAUNCH, "%ssample_ranks: zeroing the outputs failed", Head::kPrefix);
+    return G2K_OK;
+  }
   DrawnLaunch L;
   if (const int rc = drawn_launch(d, drawn_geom(*d, K), seed, Head::kPrefix, "sample_ranks", L))
     return rc;

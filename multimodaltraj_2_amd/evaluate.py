@@ -82,7 +82,15 @@ lacc (longitudinal acceleration) and straight, in the dataset's units per 0.4 s
 step — the fair CRPS, the mean PIT rank of the target among the draws (1/2 when
 calibrated; below it: the draws' feature is larger than the target's), the
 distance of the PIT histogram from uniform in --kin_bins bins, and the draws'
-and the targets' mean feature.  The units caveat above holds for a pooled
+and the targets' mean feature.  --couple_scores 1 (2 <= K <= 64) adds the
+couple-distance scores of the same K draws taken as JOINT samples, one
+g2k_couple_scores_f32 call per head in use (csrc/g2k_couples.hip; CPL_FIGURES):
+per couple of a scene-frame's members whose mean predictions come within
+--couple_reach (0: every couple) the closest approach ("min") and the final
+separation ("fin") — the fair CRPS, the mean PIT rank of the targets' among the
+draws' (1/2 when calibrated), the distance of the PIT histogram from uniform in
+--couple_bins bins, and the draws' and the targets' mean: the one proper score
+here of how the pedestrians depend on each other.  The units caveat above holds for a pooled
 fit too: eth_hotel is normalised, the UCY sets are world coordinates, so a fold
 that mixes them fits one width to both.  The build's: the reference has no probabilistic head
 (SURVEY.md §8(f) row 4), so these figures have no reference counterpart.
@@ -127,6 +135,11 @@ KIN_GROUPS = ("speed", "acc", "lacc", "straight")
 KIN_FIGURES = tuple(f"kin_{f}_{g}" for f in ("crps", "pit", "dev", "draw", "target") for g in KIN_GROUPS)
 FULLCOV_KIN_FIGURES = tuple("fullcov_" + k for k in KIN_FIGURES)
 MIX_KIN_FIGURES = tuple("mix_" + k for k in KIN_FIGURES)
+CPL_FEATURES = ("min", "fin")
+CPL_FIGURES = ("cpl_couples",) + tuple(f"cpl_{f}_{g}" for f in ("crps", "pit", "dev", "draw", "target")
+                                       for g in CPL_FEATURES)
+FULLCOV_CPL_FIGURES = tuple("fullcov_" + k for k in CPL_FIGURES)
+MIX_CPL_FIGURES = tuple("mix_" + k for k in CPL_FIGURES)
 
 
 def calib_figures(hs):
@@ -248,6 +261,26 @@ def _kin_line(name, sk, dataset, res, prefix=""):
             f"below: the draws' feature is the larger), " + ", ".join(parts))
 
 
+def couple_figures(cs, prefix=""):
+    """CPL_FIGURES (``prefix`` "fullcov_": FULLCOV_CPL_FIGURES, "mix_":
+    MIX_CPL_FIGURES) of a couples.CoupleScores."""
+    fig = {"cpl_couples": cs.couples}
+    for g in CPL_FEATURES:
+        fig.update({f"cpl_crps_{g}": cs.crps(g), f"cpl_pit_{g}": cs.pit_mean(g), f"cpl_dev_{g}": cs.dev(g),
+                    f"cpl_draw_{g}": cs.draw_mean(g), f"cpl_target_{g}": cs.target_mean(g)})
+    return {prefix + k: fig[k] for k in CPL_FIGURES}
+
+
+def _couple_line(name, cs, dataset, res, prefix=""):
+    """The log line of one head's CPL_FIGURES."""
+    parts = [f"{g} crps {res[prefix + 'cpl_crps_' + g]:.4f} pit {res[prefix + 'cpl_pit_' + g]:.4f} "
+             f"dev {res[prefix + 'cpl_dev_' + g]:.4f} draws {res[prefix + 'cpl_draw_' + g]:.4f} "
+             f"targets {res[prefix + 'cpl_target_' + g]:.4f}" for g in CPL_FEATURES]
+    return (f"{name} of the {cs.k} joint draws on dataset {dataset}: {res[prefix + 'cpl_couples']} couples "
+            f"within reach {cs.reach:g} of {cs.member_couples}, {cs.bins} bins (pit 1/2 when calibrated; "
+            f"below: the draws keep the couples further apart), " + ", ".join(parts))
+
+
 def mixture_figures(mx, bk, st, fit):
     """MIX_FIGURES of a fitted MixtureHead: its best-of-K result and
     MixtureStats on the evaluated scenes, and the MixtureFit that made it
@@ -346,6 +379,12 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
     seed) after the rank figures, and FULLCOV_KIN_FIGURES / MIX_KIN_FIGURES at
     the end of those heads' blocks, a log line each (``keep["kin"]``,
     ``keep["fullcov"]["kin"]``, ``keep["mixture"]["kin"]``).
+    --couple_scores 1 (2 <= K <= 64; --couple_bins, --couple_reach) adds
+    CPL_FIGURES from one GaussianHead.couple_scores call (csrc/g2k_couples.hip;
+    same predictions, K and seed) directly after the kinematic figures, and
+    FULLCOV_CPL_FIGURES / MIX_CPL_FIGURES after those heads' kinematic figures,
+    a log line each (``keep["couples"]``, ``keep["fullcov"]["couples"]``,
+    ``keep["mixture"]["couples"]``).
     ``keep`` (a dict)
     receives the plan, the predictions, the head and the kernels' outputs for
     a caller that checks them."""
@@ -379,6 +418,21 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
             raise ValueError(f"--kin_bins must be 0 (automatic) or a divisor of K + 1 = {K + 1} in "
                              f"1..{kn.BMAX}") from None
         kin_kw = dict(seed=args.sample_seed, want_per_ped=keep is not None)
+    want_cpl = bool(getattr(args, "couple_scores", 0))
+    if want_cpl:
+        from . import couples as cp
+        if not cp.KMIN <= K <= cp.KMAX:
+            raise ValueError("--couple_scores 1 needs --num_samples K with 2 <= K <= 64")
+        try:
+            cpl_bins = cp.check_k_bins(K, int(getattr(args, "couple_bins", 0) or 0))[1]
+        except ValueError:
+            raise ValueError(f"--couple_bins must be 0 (automatic) or a divisor of K + 1 = {K + 1} in "
+                             f"1..{cp.BMAX}") from None
+        cpl_reach = float(getattr(args, "couple_reach", 0.0) or 0.0)
+        if not cpl_reach >= 0.0:
+            raise ValueError("--couple_reach must be >= 0 (0: every couple)")
+        cpl_kw = dict(seed=args.sample_seed, reach=cpl_reach if cpl_reach > 0 else None,
+                      want_per_couple=keep is not None, want_per_frame=keep is not None)
     n_modes = int(getattr(args, "sample_modes", 0) or 0)
     if n_modes:
         if not 1 <= n_modes <= 32:
@@ -480,8 +534,14 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                             ped_mask=t["ped_mask"], **kin_kw)
         res.update(kin_figures(kin))
         log(_kin_line("sample kinematics", kin, args.leaveDataset, res))
+    cpl = None
+    if want_cpl:
+        cpl = gh.couple_scores(out.pred, t["targets"], t["n_active"], K, cpl_bins, n_frames=one,
+                               ped_mask=t["ped_mask"], **cpl_kw)
+        res.update(couple_figures(cpl))
+        log(_couple_line("couple scores", cpl, args.leaveDataset, res))
     fc_mode = getattr(args, "fullcov_head", "off") or "off"
-    fc = fc_st = fc_bk = fc_joint = fc_kde = fc_scores = fc_modes = fc_ranks = fc_kin = None
+    fc = fc_st = fc_bk = fc_joint = fc_kde = fc_scores = fc_modes = fc_ranks = fc_kin = fc_cpl = None
     if fc_mode != "off":
         from .fullcov import FullCovHead
         fc = FullCovHead(device=device)
@@ -549,8 +609,13 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                                    ped_mask=t["ped_mask"], **kin_kw)
             res.update(kin_figures(fc_kin, "fullcov_"))
             log(_kin_line("full-covariance sample kinematics", fc_kin, args.leaveDataset, res, "fullcov_"))
+        if want_cpl:
+            fc_cpl = fc.couple_scores(out.pred, t["targets"], t["n_active"], K, cpl_bins, n_frames=one,
+                                      ped_mask=t["ped_mask"], **cpl_kw)
+            res.update(couple_figures(fc_cpl, "fullcov_"))
+            log(_couple_line("full-covariance couple scores", fc_cpl, args.leaveDataset, res, "fullcov_"))
     mx_mode = getattr(args, "mixture_head", "off") or "off"
-    mx = mx_fit = mx_st = mx_bk = mx_joint = mx_kde = mx_scores = mx_modes = mx_ranks = mx_kin = None
+    mx = mx_fit = mx_st = mx_bk = mx_joint = mx_kde = mx_scores = mx_modes = mx_ranks = mx_kin = mx_cpl = None
     if mx_mode != "off":
         from .mixture import MixtureHead
         mx = MixtureHead(components=int(getattr(args, "mixture_components", 3)), device=device)
@@ -618,6 +683,11 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                                    ped_mask=t["ped_mask"], **kin_kw)
             res.update(kin_figures(mx_kin, "mix_"))
             log(_kin_line("mixture sample kinematics", mx_kin, args.leaveDataset, res, "mix_"))
+        if want_cpl:
+            mx_cpl = mx.couple_scores(out.pred, t["targets"], t["n_active"], K, cpl_bins, n_frames=one,
+                                      ped_mask=t["ped_mask"], **cpl_kw)
+            res.update(couple_figures(mx_cpl, "mix_"))
+            log(_couple_line("mixture couple scores", mx_cpl, args.leaveDataset, res, "mix_"))
     if keep is not None:
         keep.update(plan=plan, pred=out.pred, head=gh.head, out=bk, n_frames=np.ones(S, np.int32),
                     joint=joint)
@@ -635,6 +705,8 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                 keep["mixture"]["ranks"] = mx_ranks
             if mx_kin is not None:
                 keep["mixture"]["kin"] = mx_kin
+            if mx_cpl is not None:
+                keep["mixture"]["couples"] = mx_cpl
         if calibrate:
             keep.update(calib=calib, fitted=fitted)
         if kde is not None:
@@ -647,6 +719,8 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
             keep.update(ranks=ranks)
         if kin is not None:
             keep.update(kin=kin)
+        if cpl is not None:
+            keep.update(couples=cpl)
         if fc is not None:
             keep.update(fullcov=dict(stats=fc_st, out=fc_bk, fitted=ffit), fullcov_chol=fc.chol)
             if fc_joint is not None:
@@ -661,6 +735,8 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                 keep["fullcov"]["ranks"] = fc_ranks
             if fc_kin is not None:
                 keep["fullcov"]["kin"] = fc_kin
+            if fc_cpl is not None:
+                keep["fullcov"]["couples"] = fc_cpl
     return res
 
 

@@ -326,7 +326,7 @@ def _launch(lib, symbol, d, pred, targets, n_active, n_frames, ped_mask, head, s
 
 
 class SampledEvals:
-    """The seven sampled evaluations of a probabilistic head, once for the three
+    """The eight sampled evaluations of a probabilistic head, once for the three
     heads (GaussianHead below, fullcov.FullCovHead, mixture.MixtureHead): each
     is ONE launch over the K draws ``sample(pred, seed + i)``, i < k, of the
     head it is called on, none of them stored.  A head supplies ``_PREFIX``
@@ -481,6 +481,23 @@ class SampledEvals:
         return _sample_kin(self._PREFIX + "sample_kin_f32", head, d, pred, targets, n_active, k, bins,
                            seed, n_frames, ped_mask, want_per_ped, stream)
 
+    def couple_scores(self, pred, targets, n_active, k, bins=None, seed=0, *, reach=None, n_frames=None,
+                      ped_mask=None, want_per_couple=False, want_per_frame=False, targets_shared=False,
+                      stream=None):
+        """Couple-distance scores of the K JOINT draws ``sample(pred, seed +
+        i)``, i < k, in one call (``_PREFIX`` + couple_scores_f32,
+        csrc/g2k_couples.hip): per couple of a scene-frame's members whose mean
+        predictions come within ``reach`` (None: every couple) the closest
+        approach and the final separation, their fair CRPS and the targets'
+        PIT rank among the draws, uniform when the targets depend on each other
+        as the head's joint draws do -> couples.CoupleScores.  k in 2..64;
+        ``bins`` divides k + 1, at most 64 (None: the largest divisor <= 32)."""
+        from .couples import _couple_scores
+        d, head = self._sampled_inputs(pred, targets, n_active, n_frames, ped_mask, targets_shared)
+        return _couple_scores(self._PREFIX + "couple_scores_f32", head, d, pred, targets, n_active, k,
+                              bins, seed, reach, n_frames, ped_mask, want_per_couple, want_per_frame,
+                              stream)
+
 
 class GaussianHead(SampledEvals):
     """The per-step head.  Its sampled evaluations (SampledEvals) run over the
@@ -488,8 +505,9 @@ class GaussianHead(SampledEvals):
     g2k_best_of_k_f32, ``kde_nll`` g2k_kde_nll_f32, ``joint_eval``
     g2k_joint_eval_f32 (the one head that does not refuse host tensors there),
     ``sample_scores`` g2k_sample_scores_f32, ``sample_modes``
-    g2k_sample_modes_f32, ``sample_ranks`` g2k_sample_ranks_f32 and
-    ``sample_kin`` g2k_sample_kin_f32."""
+    g2k_sample_modes_f32, ``sample_ranks`` g2k_sample_ranks_f32,
+    ``sample_kin`` g2k_sample_kin_f32 and ``couple_scores``
+    g2k_couple_scores_f32."""
     _PREFIX = "g2k_"
 
     def __init__(self, log_sigma=0.0, device="cuda"):

@@ -56,7 +56,9 @@
   calibration of the K draws in --rank_bins bins, one g2k_sample_ranks_f32
   launch per head in use; with --sample_kinematics 1 also the kinematic scores
   of the K draws in --kin_bins bins, one g2k_sample_kin_f32 launch per head in
-  use).
+  use; with --couple_scores 1 also the couple-distance scores of the K joint
+  draws in --couple_bins bins within --couple_reach, one g2k_couple_scores_f32
+  call per head in use).
 
 The model weights are one seeded N(0, 1) draw (quirk Q15: the reference
 re-draws them every batch), padded to Nmax (8 for the node slice).
