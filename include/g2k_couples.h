@@ -82,7 +82,8 @@
  * round-robin to the W workgroups of a scene-frame, PASSES = ceil(TILES / W)
  * the most one of them takes; LDS_BYTES the workgroup's without the head's own
  * (the per-step head adds 192, the full-covariance head 2304, the mixture head
- * 19376).
+ * 19376, the scene-coupled head of include/g2k_coupled.h 4608: its two
+ * transposed factors).
  *
  * Alignment (bytes) of g2k_couple_scores_f32, g2k_fullcov_couple_scores_f32 and
  * g2k_mix_couple_scores_f32: targets 8, per_couple 4, per_frame_f 4,

@@ -4,7 +4,7 @@ the build's own: --data_root (Q8), --device, --mode,
 --log_dir, --save_dir, --seed, --use_grid_lstm, --loss, --num_samples,
 --sample_seed, --head_log_sigma, --collision_radius, --fit_head,
 --calibration, --fullcov_head, --mixture_head, --mixture_components,
---mixture_iters, --kde_nll, --kde_floor, --sample_scores, --sample_ranks,
+--mixture_iters, --coupled_head, --kde_nll, --kde_floor, --sample_scores, --sample_ranks,
 --rank_bins, --sample_kinematics, --kin_bins, --couple_scores, --couple_bins,
 --couple_reach, --sample_modes, --modes_draws, --modes_iters, --miss_radius."""
 import argparse
@@ -94,6 +94,15 @@ class ArgsParser:
                         metavar='1..8', help='--mixture_head: components of the mixture')
     parser.add_argument('--mixture_iters', type=int, default=30,
                         help='--mixture_head: EM iterations')
+    parser.add_argument('--coupled_head', choices=('off', 'train', 'eval'), default='off',
+                        help='--num_samples: after --mixture_head\'s figures, also fit the scene-coupled '
+                             'head (the Gaussian whose joint draws share a part among the pedestrians of '
+                             "a scene-frame; closed form) on the scenes of the fold's training datasets "
+                             '(train; honours --train_scenes) or of the left-out dataset itself (eval: '
+                             'in-sample, a bound), and report the shared part of the residual variance, '
+                             'its joint NLL per pair and what the coupling gains over the independent '
+                             'head with the same marginals; with --collision_radius / --couple_scores '
+                             'also its joint figures and couple-distance scores')
     parser.add_argument('--kde_nll', type=int, choices=(0, 1), default=0,
                         help='--num_samples K (K >= 4): 1 also reports the KDE-NLL of the K draws '
                              '(per step a Gaussian kernel density estimate of the drawn positions, '

@@ -139,7 +139,7 @@ __global__ void __launch_bounds__(kBkThreads) best_of_k_kernel(
         // of pass 0 cost registers
         size_t sb = pb;
         asm volatile("" : "+v"(sb));
-        head.draw(lo, hi, e0, Nmax, mu, [&](int t, float x, float y) {
+        head.draw(lo, hi, e0, n, Nmax, mu, [&](int t, float x, float y) {
           if (pass) {
             best[sb + (size_t)t * Nmax] = x;
             best[sb + (size_t)(kL + t) * Nmax] = y;

@@ -4,7 +4,8 @@
 // them and the two terms of the fair CRPS.  ONE kernel template,
 // couple_scores_kernel<Head, TR>, over the heads of g2k_head_draw.h
 // (g2k_couple_scores_f32, g2k_fullcov_couple_scores_f32,
-// g2k_mix_couple_scores_f32) and the two tile heights.  The C entry points are
+// g2k_mix_couple_scores_f32; g2k_coupled_couple_scores_f32 of
+// include/g2k_coupled.h) and the two tile heights.  The C entry points are
 // at the end of this file, declared in include/g2k_couples.h (added after ABI
 // 11: bound by symbol), which states the definition.  The build's: the
 // reference has no probabilistic head, so PARITY UNPINNED; pinned against
@@ -37,6 +38,7 @@
 // workgroups.
 #include "g2k_checks.h"
 #include "g2k_common.h"
+#include "g2k_coupled.h"
 #include "g2k_couples.h"
 #include "g2k_head_draw.h"
 #include "g2k_mix.h"
@@ -228,7 +230,7 @@ __global__ void __launch_bounds__(kCpThreads) couple_scores_kernel(
           if (k < K) {
             const uint32_t lo = seed_lo + (uint32_t)k;     // (seed + k) mod 2^64
             const uint32_t hi = seed_hi + (lo < seed_lo ? 1u : 0u);
-            head.draw(lo, hi, e0, Nmax, mu, [&](int t, float x, float y) {
+            head.draw(lo, hi, e0, n, Nmax, mu, [&](int t, float x, float y) {
               c[2 * t] = x; c[2 * t + 1] = y;
             });
           } else if (k == K) {
@@ -481,7 +483,7 @@ using namespace g2k;
 
 extern "C" {
 
-// the three heads share the geometry, so the workspace too
+// the heads share the geometry, so the workspace too
 int64_t g2k_couple_scores_workspace_bytes(const g2k_dims* d, int32_t K, int32_t B) {
   if (!d || !pair_sizes_ok(d) || !couples_k_ok(K) || !couples_bins_ok(B)) return -1;
   return couples_ws_bytes(d, K, B);
@@ -537,6 +539,17 @@ int g2k_mix_couple_scores_f32(const g2k_dims* d, const float* pred, const float*
   return couple_scores<MixHead>("mix_couple_scores", d, pred, targets, n_active, n_frames, ped_mask, mix,
                                 seed, K, B, reach, per_couple, per_frame_f, per_frame_i, sums, hist, tot,
                                 workspace, workspace_bytes, stream);
+}
+
+int g2k_coupled_couple_scores_f32(const g2k_dims* d, const float* pred, const float* targets,
+                                  const int32_t* n_active, const int32_t* n_frames,
+                                  const uint8_t* ped_mask, const float* cpl, uint64_t seed, int32_t K,
+                                  int32_t B, float reach, int32_t* per_couple, float* per_frame_f,
+                                  int32_t* per_frame_i, float* sums, int32_t* hist, int64_t* tot,
+                                  void* workspace, int64_t workspace_bytes, void* stream) {
+  return couple_scores<CoupledHead>("coupled_couple_scores", d, pred, targets, n_active, n_frames,
+                                    ped_mask, cpl, seed, K, B, reach, per_couple, per_frame_f,
+                                    per_frame_i, sums, hist, tot, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -7,9 +7,11 @@
 //                             taking part, a compile-time constant (the
 //                             caller's barrier follows)
 //   bind(lds)                 what a lane then draws from
-//   draw(lo, hi, e0, Nmax, mu, step)
+//   draw(lo, hi, e0, n, Nmax, mu, step)
 //                             one draw of one member for seed (hi, lo), whose
-//                             step-0 element is e0 and whose means are mu
+//                             step-0 element is e0, whose column is n (e0 - n
+//                             is the scene-frame's column-0 element: only the
+//                             coupled head looks at it) and whose means are mu
 //                             (time-major, mu[2t + c]); calls step(t, x, y) as
 //                             soon as step t's two coordinates are final
 //   kPrefix                   the head's prefix in a launcher's messages
@@ -54,7 +56,7 @@ struct PerStepHead {
     }
   }
   template <class Step>
-  __device__ __forceinline__ void draw(uint32_t lo, uint32_t hi, int64_t e0, int Nmax,
+  __device__ __forceinline__ void draw(uint32_t lo, uint32_t hi, int64_t e0, int /*n*/, int Nmax,
                                        const float (&mu)[kL2], Step&& step) const {
     const uint32_t ehi0 = (uint32_t)(e0 >> 32);
     const uint32_t stream0 = gauss_stream(lo, hi, ehi0);
@@ -123,7 +125,7 @@ struct FullCovHead {
   }
   __device__ __forceinline__ void bind(const Lds& lds) { Lt = lds.Lt; }
   template <class Step>
-  __device__ __forceinline__ void draw(uint32_t lo, uint32_t hi, int64_t e0, int Nmax,
+  __device__ __forceinline__ void draw(uint32_t lo, uint32_t hi, int64_t e0, int /*n*/, int Nmax,
                                        const float (&mu)[kL2], Step&& step) const {
     const uint32_t ehi0 = (uint32_t)(e0 >> 32);
     const uint32_t stream0 = gauss_stream(lo, hi, ehi0);
@@ -265,7 +267,7 @@ struct MixHead {
     return m;
   }
   template <class Step>
-  __device__ __forceinline__ void draw(uint32_t lo, uint32_t hi, int64_t e0, int Nmax,
+  __device__ __forceinline__ void draw(uint32_t lo, uint32_t hi, int64_t e0, int /*n*/, int Nmax,
                                        const float (&mu)[kL2], Step&& step) const {
     const uint32_t ehi0 = (uint32_t)(e0 >> 32);
     const uint32_t stream0 = gauss_stream(lo, hi, ehi0);
@@ -291,6 +293,72 @@ struct MixHead {
       for (int i = 2 * t + 2; i < kL2; ++i) asm volatile("" : "+v"(a[i]));
       step(t, a[2 * t], a[2 * t + 1]);
     }
+  }
+};
+
+// ---------------------------------------------------------------------------
+// the scene-coupled head (include/g2k_coupled.h holds the definition): cpl
+// [2][24][24] = {Lw, Lb}, the lower Cholesky factors of the covariance W of a
+// member's own part and B of the part that the members of a scene-frame share
+// ---------------------------------------------------------------------------
+// G2K_COUPLED_SALT (include/g2k_coupled.h; g2k_coupled.hip asserts the two
+// equal): the scene-frame's normals are drawn under seed XOR this
+constexpr uint32_t kCoupledSaltLo = 0x7F4A6000u, kCoupledSaltHi = 0x9E3779B9u;
+
+// The draw is FullCovHead's twice over: first the shared part c = Lb zc from
+// zeros, zc the normals of the scene-frame's column-0 element under the salted
+// seed (every member of the scene-frame forms the same c, bit for bit: 300
+// FMAs and 12 Box-Muller pairs a lane repeats, no exchange between lanes and
+// no barrier, so the policy fits every kernel that takes one); then the
+// running sums start as mu + c (one add) and the member's own steps are
+// fullcov_advance on Lw.  The first loop leaves only the 24 sums live, which
+// the second then carries: the registers of FullCovHead::draw, not twice them.
+struct CoupledHead {
+  static constexpr const char* kPrefix = "coupled_";
+  static constexpr int kJointWaveOccupancy = 2;
+  static constexpr bool kKdeRunningMean = false;
+  struct alignas(16) Lds { float Ltw[kL2 * kL2]; float Ltb[kL2 * kL2]; };
+  const float* Ltw;
+  const float* Ltb;
+
+  template <int NT>
+  static __device__ __forceinline__ void stage(const float* __restrict__ cpl, Lds& lds, int tid) {
+    fullcov_load_lt(cpl, lds.Ltw, tid, NT);
+    fullcov_load_lt(cpl + kL2 * kL2, lds.Ltb, tid, NT);
+  }
+  __device__ __forceinline__ void bind(const Lds& lds) { Ltw = lds.Ltw; Ltb = lds.Ltb; }
+  // 12 steps of fullcov_advance on Lt into a, the normals those of the element
+  // e0 + t Nmax under seed (hi, lo); FullCovHead::draw's pins
+  template <class Step>
+  static __device__ __forceinline__ void sweep(const float* Lt, uint32_t lo, uint32_t hi, int64_t e0,
+                                               int Nmax, float (&a)[kL2], Step&& step) {
+    const uint32_t ehi0 = (uint32_t)(e0 >> 32);
+    const uint32_t stream0 = gauss_stream(lo, hi, ehi0);
+    uint32_t elo0 = (uint32_t)e0;
+    asm volatile("" : "+v"(elo0));
+#pragma unroll
+    for (int t = 0; t < kL; ++t) {
+      const uint32_t elo = elo0 + (uint32_t)(t * Nmax);
+      uint32_t stream = stream0;
+      if (elo < elo0) stream = gauss_stream(lo, hi, ehi0 + 1u);   // an element that straddles 2^32
+      float z0, z1;
+      gauss_normals(stream, elo, z0, z1);
+      fullcov_advance(Lt, t, z0, z1, a);
+#pragma unroll
+      for (int i = 2 * t + 2; i < kL2; ++i) asm volatile("" : "+v"(a[i]));
+      step(t, a[2 * t], a[2 * t + 1]);
+    }
+  }
+  template <class Step>
+  __device__ __forceinline__ void draw(uint32_t lo, uint32_t hi, int64_t e0, int n, int Nmax,
+                                       const float (&mu)[kL2], Step&& step) const {
+    float a[kL2];
+#pragma unroll
+    for (int r = 0; r < kL2; ++r) a[r] = 0.f;
+    sweep(Ltb, lo ^ kCoupledSaltLo, hi ^ kCoupledSaltHi, e0 - n, Nmax, a, [](int, float, float) {});
+#pragma unroll
+    for (int r = 0; r < kL2; ++r) a[r] = mu[r] + a[r];
+    sweep(Ltw, lo, hi, e0, Nmax, a, step);
   }
 };
 

@@ -3,9 +3,10 @@
 // counts of the draws, of the mean prediction and of the targets.  ONE pair of
 // kernels, joint_kernel<Head> and joint_wave_kernel<Head>, instantiated for
 // the per-step bivariate-Gaussian head (g2k_joint_eval_f32), for the
-// full-covariance trajectory head (g2k_fullcov_joint_eval_f32) and for the
-// Gaussian-mixture head (g2k_mix_joint_eval_f32, include/g2k_mix.h); the heads
-// are the policies of g2k_head_draw.h.  The C entry points and their validator
+// full-covariance trajectory head (g2k_fullcov_joint_eval_f32), for the
+// Gaussian-mixture head (g2k_mix_joint_eval_f32, include/g2k_mix.h) and for the
+// scene-coupled head (g2k_coupled_joint_eval_f32, include/g2k_coupled.h); the
+// heads are the policies of g2k_head_draw.h.  The C entry points and their validator
 // are at the end of this file.  The build's: the reference has no
 // probabilistic head, so PARITY UNPINNED; tests/joint_ref.py restates the
 // definition over oracle/g2k_ref.py gauss_sample and tests/bestk_ref.py,
@@ -71,6 +72,7 @@
 // depend on KD.
 #include "g2k_checks.h"
 #include "g2k_common.h"
+#include "g2k_coupled.h"
 #include "g2k_head_draw.h"
 #include "g2k_mix.h"
 
@@ -150,7 +152,7 @@ __device__ __forceinline__ int pair_pass(const float4* __restrict__ buf, int P, 
 // against the targets (step t's term is taken as soon as the step is final).
 template <class Head>
 __device__ __forceinline__ void joint_coords(const Head& head, int kind, int k, const float (&mu)[kL2],
-                                             const float (&tg)[kL2], int64_t e0, int Nmax,
+                                             const float (&tg)[kL2], int64_t e0, int n, int Nmax,
                                              uint32_t seed_lo, uint32_t seed_hi, float (&c)[kL2],
                                              float& ade, float& fde) {
   if (kind != 3) {
@@ -160,7 +162,7 @@ __device__ __forceinline__ void joint_coords(const Head& head, int kind, int k, 
   }
   const uint32_t lo = seed_lo + (uint32_t)k;               // (seed + k) mod 2^64
   const uint32_t hi = seed_hi + (lo < seed_lo ? 1u : 0u);
-  head.draw(lo, hi, e0, Nmax, mu, [&](int t, float x, float y) {
+  head.draw(lo, hi, e0, n, Nmax, mu, [&](int t, float x, float y) {
     c[2 * t] = x; c[2 * t + 1] = y;
     const float dx = x - tg[2 * t], dy = y - tg[2 * t + 1];
     fde = sqrtf(fmaf(dx, dx, dy * dy));
@@ -259,7 +261,7 @@ __global__ void __launch_bounds__(kJtWaves * 64) joint_kernel(
     float ade = 0.f, fde = 0.f;
     if (on) {
       float c[kL2];
-      joint_coords(head, kind, k, mu, tg, e0, Nmax, seed_lo, seed_hi, c, ade, fde);
+      joint_coords(head, kind, k, mu, tg, e0, n, Nmax, seed_lo, seed_hi, c, ade, fde);
       joint_store(&xy[par][(size_t)tid * 6], c);
     }
     if (kind == 3) {                                       // every lane takes part in the butterfly
@@ -366,7 +368,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Head::k
     float c[kL2];
     float ade = 0.f, fde = 0.f;
     if (on && kind) {
-      joint_coords(head, kind, k, mu, tg, e0, Nmax, seed_lo, seed_hi, c, ade, fde);
+      joint_coords(head, kind, k, mu, tg, e0, n, Nmax, seed_lo, seed_hi, c, ade, fde);
       joint_store(mine + i * 6, c);
     } else {
 #pragma unroll
@@ -551,10 +553,11 @@ using namespace g2k;
 
 extern "C" {
 
-// the three heads share the geometry, so the workspace too
+// the heads share the geometry, so the workspace too
 int64_t g2k_joint_eval_workspace_bytes(const g2k_dims* d) { return joint_eval_ws_bytes(d); }
 int64_t g2k_fullcov_joint_eval_workspace_bytes(const g2k_dims* d) { return joint_eval_ws_bytes(d); }
 int64_t g2k_mix_joint_eval_workspace_bytes(const g2k_dims* d) { return joint_eval_ws_bytes(d); }
+int64_t g2k_coupled_joint_eval_workspace_bytes(const g2k_dims* d) { return joint_eval_ws_bytes(d); }
 
 // the full-covariance head's first: see g2k_bestk.hip
 int g2k_fullcov_joint_eval_f32(const g2k_dims* d, const float* pred, const float* targets,
@@ -591,6 +594,19 @@ int g2k_mix_joint_eval_f32(const g2k_dims* d, const float* pred, const float* ta
   return joint_eval<MixHead>("mix_joint_eval", d, pred, targets, n_active, n_frames, ped_mask, mix,
                              seed, K, radius, per_frame_f, per_frame_i, sums_f, sums_i, workspace,
                              workspace_bytes, stream);
+}
+
+// cpl [2][24][24] (include/g2k_coupled.h).  Every member of a scene-frame forms
+// the shared part itself from the scene-frame's own normals, so one joint
+// sample moves the members together.
+int g2k_coupled_joint_eval_f32(const g2k_dims* d, const float* pred, const float* targets,
+                               const int32_t* n_active, const int32_t* n_frames,
+                               const uint8_t* ped_mask, const float* cpl, uint64_t seed, int32_t K,
+                               float radius, float* per_frame_f, int32_t* per_frame_i, float* sums_f,
+                               int64_t* sums_i, void* workspace, int64_t workspace_bytes, void* stream) {
+  return joint_eval<CoupledHead>("coupled_joint_eval", d, pred, targets, n_active, n_frames, ped_mask,
+                                 cpl, seed, K, radius, per_frame_f, per_frame_i, sums_f, sums_i,
+                                 workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -133,7 +133,7 @@ __global__ void __launch_bounds__(kBkThreads) kde_nll_kernel(
         if constexpr (Head::kKdeRunningMean) {
           if (!pass) { cnt += 1.f; rc = 1.0f / cnt; }
         }
-        head.draw(lo, hi, e0, Nmax, mu, [&](int t, float x, float y) {
+        head.draw(lo, hi, e0, n, Nmax, mu, [&](int t, float x, float y) {
           if (!pass) {
             const float dx = x - mu[2 * t], dy = y - mu[2 * t + 1];
             if constexpr (Head::kKdeRunningMean) {

@@ -201,7 +201,7 @@ __global__ void __launch_bounds__(kKnThreads) sample_kin_kernel(
           mu[2 * t + 1] = pred[pb + (size_t)(kL + t) * Nmax];
         }
       }
-      head.draw(ln.lo, ln.hi, e0, Nmax, mu, [&](int t, float px, float py) { x.step(t, px, py); });
+      head.draw(ln.lo, ln.hi, e0, n, Nmax, mu, [&](int t, float px, float py) { x.step(t, px, py); });
       x.store(ft + tid * kKnPitch);
     } else {
 #pragma unroll

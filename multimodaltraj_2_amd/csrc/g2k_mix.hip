@@ -474,7 +474,7 @@ __global__ void __launch_bounds__(256) g2k_mix_sample_kernel(
     mu[2 * t + 1] = pred[pb + (size_t)(kL + t) * Nmax];
   }
   if (comp) comp[id] = head.select(seed_lo, seed_hi, e0);
-  head.draw(seed_lo, seed_hi, e0, Nmax, mu, [&](int t, float x, float y) {
+  head.draw(seed_lo, seed_hi, e0, n, Nmax, mu, [&](int t, float x, float y) {
     out[pb + (size_t)t * Nmax] = x;
     out[pb + (size_t)(kL + t) * Nmax] = y;
   });

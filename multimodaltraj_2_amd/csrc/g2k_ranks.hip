@@ -137,7 +137,7 @@ __global__ void __launch_bounds__(kRkThreads, 2) sample_ranks_kernel(
       const int64_t e0 = drawn_elem0(ch, sf, it.n);        // element of step 0
       float mu[kL2], tg[kL2];
       load_mu_tg(true, pred, targets, sf, shared_targets ? (size_t)s : sf, it.n, Nmax, mu, tg);
-      head.draw(ln.lo, ln.hi, e0, Nmax, mu, [&](int t, float px, float py) {
+      head.draw(ln.lo, ln.hi, e0, it.n, Nmax, mu, [&](int t, float px, float py) {
         x[2 * t] = px;
         x[2 * t + 1] = py;
       });

@@ -90,7 +90,13 @@ per couple of a scene-frame's members whose mean predictions come within
 separation ("fin") — the fair CRPS, the mean PIT rank of the targets' among the
 draws' (1/2 when calibrated), the distance of the PIT histogram from uniform in
 --couple_bins bins, and the draws' and the targets' mean: the one proper score
-here of how the pedestrians depend on each other.  The units caveat above holds for a pooled
+here of how the pedestrians depend on each other.  --coupled_head train / eval
+fits the one head that MODELS that dependence (coupled.CoupledHead,
+csrc/g2k_coupled.hip: r = c + e, c shared by the members of a scene-frame;
+closed form) and reports the shared part of the residual variance, its exact
+joint NLL per pair, what that gains over the independent head with the same
+marginals and the two calibration ratios (COUPLED_FIGURES), and with the two
+flags above its joint figures and couple-distance scores.  The units caveat above holds for a pooled
 fit too: eth_hotel is normalised, the UCY sets are world coordinates, so a fold
 that mixes them fits one width to both.  The build's: the reference has no probabilistic head
 (SURVEY.md §8(f) row 4), so these figures have no reference counterpart.
@@ -140,6 +146,25 @@ CPL_FIGURES = ("cpl_couples",) + tuple(f"cpl_{f}_{g}" for f in ("crps", "pit", "
                                        for g in CPL_FEATURES)
 FULLCOV_CPL_FIGURES = tuple("fullcov_" + k for k in CPL_FIGURES)
 MIX_CPL_FIGURES = tuple("mix_" + k for k in CPL_FIGURES)
+COUPLED_FIGURES = ("coupled_share", "coupled_nll", "coupled_nll_gain", "coupled_q_within", "coupled_q_between",
+                   "coupled_clipped")
+COUPLED_JOINT_FIGURES = ("coupled_jade", "coupled_jfde", "coupled_collision_rate",
+                         "coupled_collision_rate_best")
+COUPLED_CPL_FIGURES = tuple("coupled_" + k for k in CPL_FIGURES)
+
+
+def coupled_figures(head, st):
+    """COUPLED_FIGURES of a fitted coupled.CoupledHead and its CoupledStats on
+    the left-out scenes."""
+    return dict(coupled_share=st.share, coupled_nll=st.nll, coupled_nll_gain=st.nll_gain,
+                coupled_q_within=st.q_within_ratio, coupled_q_between=st.q_between_ratio,
+                coupled_clipped=head.clipped)
+
+
+def coupled_joint_figures(je):
+    """COUPLED_JOINT_FIGURES of a CoupledHead.joint_eval result."""
+    return dict(coupled_jade=je.jade, coupled_jfde=je.jfde, coupled_collision_rate=je.collision_rate,
+                coupled_collision_rate_best=je.collision_rate_best)
 
 
 def calib_figures(hs):
@@ -385,6 +410,13 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
     FULLCOV_CPL_FIGURES / MIX_CPL_FIGURES after those heads' kinematic figures,
     a log line each (``keep["couples"]``, ``keep["fullcov"]["couples"]``,
     ``keep["mixture"]["couples"]``).
+    --coupled_head train / eval then fits the scene-coupled head
+    (coupled.CoupledHead, csrc/g2k_coupled.hip: closed form) on the same
+    scenes as --fullcov_head's modes and adds COUPLED_FIGURES from one stats
+    launch on the left-out scenes and a log line; with --collision_radius R >
+    0 also COUPLED_JOINT_FIGURES and with --couple_scores 1
+    COUPLED_CPL_FIGURES, one launch and one log line each
+    (``keep["coupled"]``).
     ``keep`` (a dict)
     receives the plan, the predictions, the head and the kernels' outputs for
     a caller that checks them."""
@@ -688,7 +720,51 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                                       ped_mask=t["ped_mask"], **cpl_kw)
             res.update(couple_figures(mx_cpl, "mix_"))
             log(_couple_line("mixture couple scores", mx_cpl, args.leaveDataset, res, "mix_"))
+    co_mode = getattr(args, "coupled_head", "off") or "off"
+    co = co_fit = co_st = co_joint = co_cpl = None
+    if co_mode != "off":
+        from .coupled import CoupledHead
+        co = CoupledHead(device=device)
+        if co_mode == "train":
+            fplan = fold_plan(args, params.nmax)
+            ft, fout, fone = _fused_step(args, params, fplan, device)
+            co_fit = co.fit(fout.pred, ft["targets"], ft["n_active"], n_frames=fone, ped_mask=ft["ped_mask"])
+            where = (f"{fplan.S} scenes of the fold's training datasets ({co_fit.pairs} pairs in "
+                     f"{co_fit.groups} scene-frames)")
+        else:
+            co_fit = co.fit(out.pred, t["targets"], t["n_active"], n_frames=one, ped_mask=t["ped_mask"])
+            where = (f"the left-out dataset itself ({co_fit.pairs} pairs in {co_fit.groups} scene-frames): "
+                     f"in-sample, a bound and not an estimate")
+        co_st = co.stats(out.pred, t["targets"], t["n_active"], n_frames=one, ped_mask=t["ped_mask"])
+        res.update(coupled_figures(co, co_st))
+        log(f"coupled head on dataset {args.leaveDataset}: closed-form fit on {where}, "
+            f"{res['coupled_clipped']} eigenvalues clipped; shared part of the residual variance "
+            f"{res['coupled_share']:.4f}, joint NLL per pair {res['coupled_nll']:.6g}, "
+            f"{res['coupled_nll_gain']:.6g} nats below the independent head with the same marginals, "
+            f"q_within {res['coupled_q_within']:.6g} q_between {res['coupled_q_between']:.6g} (1 when "
+            f"calibrated; left-out scenes)")
+        if radius > 0:
+            co_joint = co.joint_eval(out.pred, t["targets"], t["n_active"], K, radius, seed=args.sample_seed,
+                                     n_frames=one, ped_mask=t["ped_mask"], want_per_frame=keep is not None)
+            res.update(coupled_joint_figures(co_joint))
+            log(f"coupled joint best-of-K on dataset {args.leaveDataset}: radius {radius:g}, "
+                f"K {K}, JADE_{K} {res['coupled_jade']:.6g} JFDE_{K} {res['coupled_jfde']:.6g} "
+                f"(per-step head {res['jade']:.6g} / {res['jfde']:.6g}), collision rate: samples "
+                f"{res['coupled_collision_rate']:.6g} (per-step head {res['collision_rate']:.6g}) "
+                f"best joint sample {res['coupled_collision_rate_best']:.6g} (per-step head "
+                f"{res['collision_rate_best']:.6g})")
+        if want_cpl:
+            co_cpl = co.couple_scores(out.pred, t["targets"], t["n_active"], K, cpl_bins, n_frames=one,
+                                      ped_mask=t["ped_mask"], **cpl_kw)
+            res.update(couple_figures(co_cpl, "coupled_"))
+            log(_couple_line("coupled couple scores", co_cpl, args.leaveDataset, res, "coupled_"))
     if keep is not None:
+        if co is not None:
+            keep.update(coupled=dict(head=co, fit=co_fit, stats=co_st))
+            if co_joint is not None:
+                keep["coupled"]["joint"] = co_joint
+            if co_cpl is not None:
+                keep["coupled"]["couples"] = co_cpl
         keep.update(plan=plan, pred=out.pred, head=gh.head, out=bk, n_frames=np.ones(S, np.int32),
                     joint=joint)
         if mx is not None:
