@@ -88,11 +88,19 @@
  * coupled twin: one member's law is N(mu, W + B), so those figures are a
  * full-covariance head's with chol(W + B).
  *
+ * g2k_coupled_scene_ranks_f32: the arguments, outputs, checks and workspace
+ * query of g2k_fullcov_scene_ranks_f32 (include/g2k_scene_ranks.h;
+ * g2k_scene_ranks_workspace_bytes is one size for every head) with cpl in
+ * place of chol, over the same joint samples: the scene-level rank calibration
+ * is the figure that says whether the coupling is too weak or too strong.
+ *
  * Alignment (bytes).  g2k_coupled_stats_f32: targets 8, whiten 8, within 8,
  * between 8, counts 8, stats 8, workspace 8.  g2k_coupled_sample_f32: pred 4,
  * cpl 4, out 4.  g2k_coupled_joint_eval_f32: targets 8, sums_i 8, workspace 4.
  * g2k_coupled_couple_scores_f32: targets 8, per_couple 4, per_frame_f 4,
  * per_frame_i 4, sums 4, hist 4, tot 8, workspace 4.
+ * g2k_coupled_scene_ranks_f32: targets 8, per_frame_i 4, per_frame_d 8, sums 8,
+ * hist 4, tot 8, workspace 8.
  */
 #ifndef G2K_COUPLED_H_
 #define G2K_COUPLED_H_
@@ -127,6 +135,12 @@ int g2k_coupled_couple_scores_f32(const g2k_dims* d, const float* pred, const fl
                                   int32_t B, float reach, int32_t* per_couple, float* per_frame_f,
                                   int32_t* per_frame_i, float* sums, int32_t* hist, int64_t* tot,
                                   void* workspace, int64_t workspace_bytes, void* stream);
+int g2k_coupled_scene_ranks_f32(const g2k_dims* d, const float* pred, const float* targets,
+                                const int32_t* n_active, const int32_t* n_frames,
+                                const uint8_t* ped_mask, const float* cpl, uint64_t seed, int32_t K,
+                                int32_t B, int32_t* per_frame_i, double* per_frame_d, double* sums,
+                                int32_t* hist, int64_t* tot, void* workspace, int64_t workspace_bytes,
+                                void* stream);
 
 #ifdef __cplusplus
 }

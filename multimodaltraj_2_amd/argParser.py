@@ -6,7 +6,7 @@ the build's own: --data_root (Q8), --device, --mode,
 --calibration, --fullcov_head, --mixture_head, --mixture_components,
 --mixture_iters, --coupled_head, --kde_nll, --kde_floor, --sample_scores, --sample_ranks,
 --rank_bins, --sample_kinematics, --kin_bins, --couple_scores, --couple_bins,
---couple_reach, --sample_modes, --modes_draws, --modes_iters, --miss_radius."""
+--couple_reach, --scene_ranks, --scene_bins, --sample_modes, --modes_draws, --modes_iters, --miss_radius."""
 import argparse
 
 
@@ -149,6 +149,17 @@ class ArgsParser:
                         help="--couple_scores: score the couples whose mean predictions come closer "
                              "than this, in the dataset's own units as --collision_radius (0: every "
                              'couple)')
+    parser.add_argument('--scene_ranks', type=int, choices=(0, 1), default=0,
+                        help='--num_samples K (2 <= K <= 64): 1 also reports the scene-level rank '
+                             "calibration of the K draws taken as joint samples (a scene's targets "
+                             'ranked among the draws by typicality, common mode and within-scene '
+                             "spread: the rank histograms' distance from uniform and the mean PIT, "
+                             "the draws' and the targets' mean feature, and the fair energy score of "
+                             "the scene's joint law), of the per-step head and, with --fullcov_head / "
+                             '--mixture_head / --coupled_head, of those heads')
+    parser.add_argument('--scene_bins', type=int, default=0,
+                        help='--scene_ranks: bins of the rank histograms, a divisor of K + 1 up to 64 '
+                             '(0: the largest divisor <= 32)')
     parser.add_argument('--sample_modes', type=int, default=0,
                         help='--num_samples: M in 1..32 also reduces --modes_draws draws of each head '
                              'in use to M representative trajectories with probabilities (k-means '

@@ -16,8 +16,8 @@ NLL of the independent head with the same marginals: their difference is what
 the coupling is worth in nats.  ``fit`` is the closed-form method-of-moments
 estimate (one stats launch, then a 24 x 24 projection in float64 on the host),
 ``sample`` draws one reproducible joint trajectory set, and ``joint_eval`` /
-``couple_scores`` are nll.SampledEvals' over this head's joint draws, one launch
-each.  The per-pedestrian evaluations belong to ``marginal()``.
+``couple_scores`` / ``scene_ranks`` are nll.SampledEvals' over this head's joint
+draws, one call each.  The per-pedestrian evaluations belong to ``marginal()``.
 
 The entry points were added after ABI 11 and are declared in a header of their
 own, so this module binds them itself on the handle ``_lib.load()`` returns
@@ -31,7 +31,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib, couples
+from . import _lib, couples, sceneranks
 from .frame_step import PRED_LEN, _check_dev, _ptr, _stream
 from .nll import SampledEvals, _check_pairs_inputs
 
@@ -52,6 +52,7 @@ SYMBOLS = {
     "g2k_coupled_joint_eval_f32": (_int, [_D, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _i32, ctypes.c_float, _vp,
                                           _vp, _vp, _vp, _vp, _i64, _vp]),
     "g2k_coupled_couple_scores_f32": couples._CPL,
+    "g2k_coupled_scene_ranks_f32": sceneranks._SCN,
 }
 
 
@@ -190,10 +191,11 @@ class CoupledStats:
 
 
 class CoupledHead(SampledEvals):
-    """The scene-coupled head.  Of nll.SampledEvals it has the two evaluations
-    of JOINT draws, ``joint_eval`` (g2k_coupled_joint_eval_f32) and
-    ``couple_scores`` (g2k_coupled_couple_scores_f32), GPU tensors only; the
-    per-pedestrian ones raise: they are ``marginal()``'s."""
+    """The scene-coupled head.  Of nll.SampledEvals it has the three
+    evaluations of JOINT draws, ``joint_eval`` (g2k_coupled_joint_eval_f32),
+    ``couple_scores`` (g2k_coupled_couple_scores_f32) and ``scene_ranks``
+    (g2k_coupled_scene_ranks_f32), GPU tensors only; the per-pedestrian ones
+    raise: they are ``marginal()``'s."""
     _PREFIX = "g2k_coupled_"
     _JOINT_GPU_ONLY = True
 

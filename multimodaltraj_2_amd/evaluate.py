@@ -90,7 +90,13 @@ per couple of a scene-frame's members whose mean predictions come within
 separation ("fin") — the fair CRPS, the mean PIT rank of the targets' among the
 draws' (1/2 when calibrated), the distance of the PIT histogram from uniform in
 --couple_bins bins, and the draws' and the targets' mean: the one proper score
-here of how the pedestrians depend on each other.  --coupled_head train / eval
+here of how the pedestrians depend on each other.  --scene_ranks 1 (2 <= K <=
+64) adds the scene-level rank calibration of the same joint draws, one
+g2k_scene_ranks_f32 call per head in use (csrc/g2k_scene_ranks.hip;
+SCN_FIGURES): the targets' whole configuration of a scene ranked among the
+draws' by typicality, common mode and within-scene spread in --scene_bins bins,
+and the fair energy score of the scene's joint law, which is reported and never
+gated on (it hardly sees dependence).  --coupled_head train / eval
 fits the one head that MODELS that dependence (coupled.CoupledHead,
 csrc/g2k_coupled.hip: r = c + e, c shared by the members of a scene-frame;
 closed form) and reports the shared part of the residual variance, its exact
@@ -146,6 +152,12 @@ CPL_FIGURES = ("cpl_couples",) + tuple(f"cpl_{f}_{g}" for f in ("crps", "pit", "
                                        for g in CPL_FEATURES)
 FULLCOV_CPL_FIGURES = tuple("fullcov_" + k for k in CPL_FIGURES)
 MIX_CPL_FIGURES = tuple("mix_" + k for k in CPL_FIGURES)
+SCN_FEATURES = ("typ", "loc", "spr")
+SCN_FIGURES = (("scn_frames", "scn_es") + tuple(f"scn_{f}_{g}" for g in SCN_FEATURES for f in ("dev", "pit"))
+               + ("scn_draw_loc", "scn_target_loc", "scn_draw_spr", "scn_target_spr"))
+FULLCOV_SCN_FIGURES = tuple("fullcov_" + k for k in SCN_FIGURES)
+MIX_SCN_FIGURES = tuple("mix_" + k for k in SCN_FIGURES)
+COUPLED_SCN_FIGURES = tuple("coupled_" + k for k in SCN_FIGURES)
 COUPLED_FIGURES = ("coupled_share", "coupled_nll", "coupled_nll_gain", "coupled_q_within", "coupled_q_between",
                    "coupled_clipped")
 COUPLED_JOINT_FIGURES = ("coupled_jade", "coupled_jfde", "coupled_collision_rate",
@@ -296,6 +308,30 @@ def couple_figures(cs, prefix=""):
     return {prefix + k: fig[k] for k in CPL_FIGURES}
 
 
+def scene_figures(sr, prefix=""):
+    """SCN_FIGURES (``prefix`` "fullcov_", "mix_", "coupled_": those heads') of
+    a sceneranks.SceneRanks."""
+    fig = {"scn_frames": sr.frames, "scn_es": sr.es}
+    for g in SCN_FEATURES:
+        fig.update({f"scn_dev_{g}": sr.dev(g), f"scn_pit_{g}": sr.pit(g)})
+    for g in SCN_FEATURES[1:]:
+        fig.update({f"scn_draw_{g}": sr.draw(g), f"scn_target_{g}": sr.target(g)})
+    return {prefix + k: fig[k] for k in SCN_FIGURES}
+
+
+def _scene_line(name, sr, dataset, res, prefix=""):
+    """The log line of one head's SCN_FIGURES."""
+    parts = [f"{g} dev {res[prefix + 'scn_dev_' + g]:.4f} pit {res[prefix + 'scn_pit_' + g]:.4f}"
+             for g in SCN_FEATURES]
+    parts += [f"{g} draws {res[prefix + 'scn_draw_' + g]:.4f} targets {res[prefix + 'scn_target_' + g]:.4f}"
+              for g in SCN_FEATURES[1:]]
+    return (f"{name} of the {sr.k} joint draws on dataset {dataset}: {res[prefix + 'scn_frames']} scenes of "
+            f"two pedestrians or more, {sr.bins} bins (pit 1/2 when calibrated; loc near 1 and spr near 0: "
+            f"the pedestrians move together more than the draws do), fair energy score "
+            f"{res[prefix + 'scn_es']:.6g} (nearly blind to dependence: reported, never gated on), "
+            + ", ".join(parts))
+
+
 def _couple_line(name, cs, dataset, res, prefix=""):
     """The log line of one head's CPL_FIGURES."""
     parts = [f"{g} crps {res[prefix + 'cpl_crps_' + g]:.4f} pit {res[prefix + 'cpl_pit_' + g]:.4f} "
@@ -410,6 +446,11 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
     FULLCOV_CPL_FIGURES / MIX_CPL_FIGURES after those heads' kinematic figures,
     a log line each (``keep["couples"]``, ``keep["fullcov"]["couples"]``,
     ``keep["mixture"]["couples"]``).
+    --scene_ranks 1 (2 <= K <= 64; --scene_bins) adds SCN_FIGURES directly
+    after the same head's couple-distance figures, from one
+    ``scene_ranks`` call per head in use (csrc/g2k_scene_ranks.hip), the
+    other heads' prefixed "fullcov_" / "mix_" / "coupled_", a log line each
+    (``keep["scene_ranks"]``, ``keep[<head>]["scene_ranks"]``).
     --coupled_head train / eval then fits the scene-coupled head
     (coupled.CoupledHead, csrc/g2k_coupled.hip: closed form) on the same
     scenes as --fullcov_head's modes and adds COUPLED_FIGURES from one stats
@@ -465,6 +506,17 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
             raise ValueError("--couple_reach must be >= 0 (0: every couple)")
         cpl_kw = dict(seed=args.sample_seed, reach=cpl_reach if cpl_reach > 0 else None,
                       want_per_couple=keep is not None, want_per_frame=keep is not None)
+    want_scn = bool(getattr(args, "scene_ranks", 0))
+    if want_scn:
+        from . import sceneranks as sn
+        if not sn.KMIN <= K <= sn.KMAX:
+            raise ValueError("--scene_ranks 1 needs --num_samples K with 2 <= K <= 64")
+        try:
+            scn_bins = sn.check_k_bins(K, int(getattr(args, "scene_bins", 0) or 0))[1]
+        except ValueError:
+            raise ValueError(f"--scene_bins must be 0 (automatic) or a divisor of K + 1 = {K + 1} in "
+                             f"1..{sn.BMAX}") from None
+        scn_kw = dict(seed=args.sample_seed, want_per_frame=keep is not None)
     n_modes = int(getattr(args, "sample_modes", 0) or 0)
     if n_modes:
         if not 1 <= n_modes <= 32:
@@ -572,8 +624,14 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                                ped_mask=t["ped_mask"], **cpl_kw)
         res.update(couple_figures(cpl))
         log(_couple_line("couple scores", cpl, args.leaveDataset, res))
+    scn = None
+    if want_scn:
+        scn = gh.scene_ranks(out.pred, t["targets"], t["n_active"], K, scn_bins, n_frames=one,
+                             ped_mask=t["ped_mask"], **scn_kw)
+        res.update(scene_figures(scn))
+        log(_scene_line("scene ranks", scn, args.leaveDataset, res))
     fc_mode = getattr(args, "fullcov_head", "off") or "off"
-    fc = fc_st = fc_bk = fc_joint = fc_kde = fc_scores = fc_modes = fc_ranks = fc_kin = fc_cpl = None
+    fc = fc_st = fc_bk = fc_joint = fc_kde = fc_scores = fc_modes = fc_ranks = fc_kin = fc_cpl = fc_scn = None
     if fc_mode != "off":
         from .fullcov import FullCovHead
         fc = FullCovHead(device=device)
@@ -646,8 +704,13 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                                       ped_mask=t["ped_mask"], **cpl_kw)
             res.update(couple_figures(fc_cpl, "fullcov_"))
             log(_couple_line("full-covariance couple scores", fc_cpl, args.leaveDataset, res, "fullcov_"))
+        if want_scn:
+            fc_scn = fc.scene_ranks(out.pred, t["targets"], t["n_active"], K, scn_bins, n_frames=one,
+                                    ped_mask=t["ped_mask"], **scn_kw)
+            res.update(scene_figures(fc_scn, "fullcov_"))
+            log(_scene_line("full-covariance scene ranks", fc_scn, args.leaveDataset, res, "fullcov_"))
     mx_mode = getattr(args, "mixture_head", "off") or "off"
-    mx = mx_fit = mx_st = mx_bk = mx_joint = mx_kde = mx_scores = mx_modes = mx_ranks = mx_kin = mx_cpl = None
+    mx = mx_fit = mx_st = mx_bk = mx_joint = mx_kde = mx_scores = mx_modes = mx_ranks = mx_kin = mx_cpl = mx_scn = None
     if mx_mode != "off":
         from .mixture import MixtureHead
         mx = MixtureHead(components=int(getattr(args, "mixture_components", 3)), device=device)
@@ -720,8 +783,13 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                                       ped_mask=t["ped_mask"], **cpl_kw)
             res.update(couple_figures(mx_cpl, "mix_"))
             log(_couple_line("mixture couple scores", mx_cpl, args.leaveDataset, res, "mix_"))
+        if want_scn:
+            mx_scn = mx.scene_ranks(out.pred, t["targets"], t["n_active"], K, scn_bins, n_frames=one,
+                                    ped_mask=t["ped_mask"], **scn_kw)
+            res.update(scene_figures(mx_scn, "mix_"))
+            log(_scene_line("mixture scene ranks", mx_scn, args.leaveDataset, res, "mix_"))
     co_mode = getattr(args, "coupled_head", "off") or "off"
-    co = co_fit = co_st = co_joint = co_cpl = None
+    co = co_fit = co_st = co_joint = co_cpl = co_scn = None
     if co_mode != "off":
         from .coupled import CoupledHead
         co = CoupledHead(device=device)
@@ -758,6 +826,11 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                                       ped_mask=t["ped_mask"], **cpl_kw)
             res.update(couple_figures(co_cpl, "coupled_"))
             log(_couple_line("coupled couple scores", co_cpl, args.leaveDataset, res, "coupled_"))
+        if want_scn:
+            co_scn = co.scene_ranks(out.pred, t["targets"], t["n_active"], K, scn_bins, n_frames=one,
+                                    ped_mask=t["ped_mask"], **scn_kw)
+            res.update(scene_figures(co_scn, "coupled_"))
+            log(_scene_line("coupled scene ranks", co_scn, args.leaveDataset, res, "coupled_"))
     if keep is not None:
         if co is not None:
             keep.update(coupled=dict(head=co, fit=co_fit, stats=co_st))
@@ -765,6 +838,8 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                 keep["coupled"]["joint"] = co_joint
             if co_cpl is not None:
                 keep["coupled"]["couples"] = co_cpl
+            if co_scn is not None:
+                keep["coupled"]["scene_ranks"] = co_scn
         keep.update(plan=plan, pred=out.pred, head=gh.head, out=bk, n_frames=np.ones(S, np.int32),
                     joint=joint)
         if mx is not None:
@@ -783,6 +858,8 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                 keep["mixture"]["kin"] = mx_kin
             if mx_cpl is not None:
                 keep["mixture"]["couples"] = mx_cpl
+            if mx_scn is not None:
+                keep["mixture"]["scene_ranks"] = mx_scn
         if calibrate:
             keep.update(calib=calib, fitted=fitted)
         if kde is not None:
@@ -797,6 +874,8 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
             keep.update(kin=kin)
         if cpl is not None:
             keep.update(couples=cpl)
+        if scn is not None:
+            keep.update(scene_ranks=scn)
         if fc is not None:
             keep.update(fullcov=dict(stats=fc_st, out=fc_bk, fitted=ffit), fullcov_chol=fc.chol)
             if fc_joint is not None:
@@ -813,6 +892,8 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                 keep["fullcov"]["kin"] = fc_kin
             if fc_cpl is not None:
                 keep["fullcov"]["couples"] = fc_cpl
+            if fc_scn is not None:
+                keep["fullcov"]["scene_ranks"] = fc_scn
     return res
 
 

@@ -326,8 +326,9 @@ def _launch(lib, symbol, d, pred, targets, n_active, n_frames, ped_mask, head, s
 
 
 class SampledEvals:
-    """The eight sampled evaluations of a probabilistic head, once for the three
-    heads (GaussianHead below, fullcov.FullCovHead, mixture.MixtureHead): each
+    """The nine sampled evaluations of a probabilistic head, once for the
+    heads (GaussianHead below, fullcov.FullCovHead, mixture.MixtureHead;
+    coupled.CoupledHead takes the three of JOINT draws): each
     is ONE launch over the K draws ``sample(pred, seed + i)``, i < k, of the
     head it is called on, none of them stored.  A head supplies ``_PREFIX``
     (its entry points are ``_PREFIX`` + best_of_k_f32, ...), ``_head_tensor``
@@ -497,6 +498,21 @@ class SampledEvals:
         return _couple_scores(self._PREFIX + "couple_scores_f32", head, d, pred, targets, n_active, k,
                               bins, seed, reach, n_frames, ped_mask, want_per_couple, want_per_frame,
                               stream)
+
+    def scene_ranks(self, pred, targets, n_active, k, bins=None, seed=0, *, n_frames=None, ped_mask=None,
+                    targets_shared=False, want_per_frame=False, stream=None):
+        """Scene-level rank calibration of the K JOINT draws ``sample(pred,
+        seed + i)``, i < k, in one call (``_PREFIX`` + scene_ranks_f32,
+        csrc/g2k_scene_ranks.hip): per scene-frame with two members or more
+        the targets' whole configuration ranked among the draws' by
+        typicality, common mode and within-scene spread, uniform when the
+        targets come from the head's joint law, and the fair energy score of
+        that law -> sceneranks.SceneRanks.  GPU tensors only.  k in 2..64;
+        ``bins`` divides k + 1, at most 64 (None: the largest divisor <= 32)."""
+        from .sceneranks import _scene_ranks
+        d, head = self._sampled_inputs(pred, targets, n_active, n_frames, ped_mask, targets_shared)
+        return _scene_ranks(self._PREFIX + "scene_ranks_f32", head, d, pred, targets, n_active, k, bins,
+                            seed, n_frames, ped_mask, want_per_frame, stream)
 
 
 class GaussianHead(SampledEvals):

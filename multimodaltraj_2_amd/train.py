@@ -58,7 +58,9 @@
   of the K draws in --kin_bins bins, one g2k_sample_kin_f32 launch per head in
   use; with --couple_scores 1 also the couple-distance scores of the K joint
   draws in --couple_bins bins within --couple_reach, one g2k_couple_scores_f32
-  call per head in use).
+  call per head in use; with --scene_ranks 1 also the scene-level rank
+  calibration of the K joint draws in --scene_bins bins, one
+  g2k_scene_ranks_f32 call per head in use).
 
 The model weights are one seeded N(0, 1) draw (quirk Q15: the reference
 re-draws them every batch), padded to Nmax (8 for the node slice).
