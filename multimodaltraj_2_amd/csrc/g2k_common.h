@@ -142,6 +142,32 @@ __device__ __forceinline__ float partner32(float v) {
   return a[0] == __float_as_uint(v) ? __uint_as_float(a[1]) : __uint_as_float(a[0]);
 }
 
+// max(v, partner's v) with no compare or select: the swap's two outputs ARE
+// the lane's own value and its partner's, in either order.
+__device__ __forceinline__ float pair_max16(float v) {
+  auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
+}
+__device__ __forceinline__ float pair_max32(float v) {
+  auto a = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
+}
+// partner16 / partner32 selected by the lane's group q = lane >> 4 instead of a
+// compare with the lane's own value (the masks q & 1, q & 2 are lane
+// constants, formed once per wave): permlane16_swap(x, y) returns {[x.r0,
+// y.r0, x.r2, y.r2], [x.r1, y.r1, x.r3, y.r3]} by 16-lane rows, so with x = y
+// the odd rows find their partner in [0], the even rows in [1];
+// permlane32_swap(x, y) returns {[x.lo, y.lo], [x.hi, y.hi]} by 32-lane
+// halves: the upper half's partner is in [0], the lower half's in [1].
+__device__ __forceinline__ float partner16_q(float v, int q) {
+  auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return __uint_as_float((q & 1) ? a[0] : a[1]);
+}
+__device__ __forceinline__ float partner32_q(float v, int q) {
+  auto a = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return __uint_as_float((q & 2) ? a[0] : a[1]);
+}
+
 // Sum over all 64 lanes (DPP + permlane, no LDS); every lane gets the result.
 __device__ __forceinline__ float wave_sum(float v) { return sum_rows4(row16_sum(v)); }
 // ... of an int (lane shuffles)

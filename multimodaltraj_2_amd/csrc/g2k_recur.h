@@ -407,34 +407,53 @@ struct RecurH {
   // lane's wave (lane L holds wave L % NW's), b = As[L][4q..4q+3] * log2(e)
   // of this frame, last: the scene's last frame (accumulator from 0).  The
   // B operands of the next frame are split after the sequence word is out.
+  //
+  // seed: the accumulators' start, a register quad of -kOff the caller holds
+  // across its frame loops; the scene's last frame zeroes it first, under a
+  // wave-uniform branch (the asm keeps the branch a branch), so no other
+  // frame selects, rebuilds or copies a seed.
+  //
+  // Row sums: after two quad exchanges every lane of a quad would hold the
+  // same four sums (w0 + w1) + (w2 + w3); instead a transposing butterfly
+  // (reduce4_rows16's first two stages) leaves lane j of the quad with the
+  // sum of row reduce4_row(j) alone, in the same order of additions (the
+  // operands of an addition swapped at most: the same bits), so a lane takes
+  // ONE reciprocal and the four products b_i / Z_i read it from the quad's
+  // lane by the multiply's DPP operand.
   __device__ __forceinline__ void step_seq(const float4 b, const f32x4 zq, float* red_nxt,
                                            int* seq, int seq_val, int wv, int q, int L,
                                            const int* pf_flag, const float* pf_as, int& pf_fl,
-                                           float4& pf_b, bool last) {
+                                           float4& pf_b, f32x4& seed, bool last) {
     int fl;
     f32x4 v;
     asm volatile("ds_read_b32 %0, %2\n\tds_read_b128 %1, %3"
                  : "=&v"(fl), "=&v"(v)
                  : "v"(lds_addr(pf_flag)), "v"(lds_addr(pf_as))
                  : "memory");
-    float z[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float t = zq[i];
-      t += dpp<0xB1>(t);                     // quad_perm [1,0,3,2]
-      t += dpp<0x4E>(t);                     // quad_perm [2,3,0,1]
+    float rz;
+    {
+      const bool odd = (L & 1) != 0, b1 = (L & 2) != 0;
+      const float s0 = odd ? zq[0] : zq[2], s1 = odd ? zq[1] : zq[3];   // rows the xor-1 partner keeps
+      const float a0 = (odd ? zq[2] : zq[0]) + dpp<0xB1>(s0);         // quad_perm [1,0,3,2]
+      const float a1 = (odd ? zq[3] : zq[1]) + dpp<0xB1>(s1);
+      float t = (b1 ? a1 : a0) + dpp<0x4E>(b1 ? a0 : a1);             // quad_perm [2,3,0,1]
       if constexpr (NW == 8) t += dpp<0x124>(t);   // row_ror:4 (the other quad's four waves)
-      z[i] = t;
+      rz = rcp(t);                                 // 1 / Z of row 4q' + reduce4_row(L), q' = this quad's
     }
-    const u32x4v A = split4(b.x * rcp(z[0]), b.y * rcp(z[1]), b.z * rcp(z[2]), b.w * rcp(z[3]));
+    // rows 0, 1, 2, 3 sit in the quad's lanes 0, 2, 1, 3 (reduce4_row)
+    const u32x4v A = split4(b.x * dpp<0x00>(rz), b.y * dpp<0xAA>(rz), b.z * dpp<0x55>(rz),
+                            b.w * dpp<0xFF>(rz));
     const u32x4v A2 = {A[2], A[3], A[0], A[1]};
-    const float c0 = last ? 0.f : -kOff;
+    if (last) {
+      seed = f32x4{0.f, 0.f, 0.f, 0.f};
+      asm volatile("" : "+v"(seed));
+    }
     __builtin_amdgcn_sched_barrier(0);
     f32x4 acc[TPW];
 #pragma unroll
     for (int t = 0; t < TPW; ++t)
       acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, A), __builtin_bit_cast(f16x8, bo[t]),
-                                                      f32x4{c0, c0, c0, c0}, 0, 0, 0);
+                                                      seed, 0, 0, 0);
 #pragma unroll
     for (int t = 0; t < TPW; ++t)
       acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, A2), __builtin_bit_cast(f16x8, bo[t]),

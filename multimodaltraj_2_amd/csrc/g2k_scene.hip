@@ -250,15 +250,15 @@ struct FrameHeadOut {
 // values in (0, 1].  Stored as As * log2(e): the recurrence's A operand.
 __device__ __forceinline__ void attn_weights(const f32x4 aA, float* as_dst, int L, int q) {
   float mx = fmaxf(fmaxf(aA[0], aA[1]), fmaxf(aA[2], aA[3]));
-  mx = fmaxf(mx, partner16(mx));
-  mx = fmaxf(mx, partner32(mx));
+  mx = pair_max16(mx);   // the column maximum: max of each swap's two outputs
+  mx = pair_max32(mx);
   float e[4], p[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) e[i] = __expf(aA[i] - mx);
   p[0] = e[0];
 #pragma unroll
   for (int i = 1; i < 4; ++i) p[i] = p[i - 1] + e[i];
-  const float t1 = partner16(p[3]), t2 = partner32(p[3]), t3 = partner32(t1);
+  const float t1 = partner16_q(p[3], q), t2 = partner32_q(p[3], q), t3 = partner32_q(t1, q);
   const float pre = ((q & 2) ? t2 + t3 : 0.f) + ((q & 1) ? t1 : 0.f);   // groups before q
   float R[4];
   bool bad = false;
@@ -762,6 +762,11 @@ __device__ __forceinline__ void scene_recurrence(const StepArgs& a, const SceneL
   const int H = a.d.H;
   const bool live = a.h_in != nullptr && c.x == 0;   // (the scene's first workgroup)
   RecurH<TPW, kRecW> rc;
+  // the accumulator seed of every frame but the scene's last (which zeroes
+  // it): one register quad for all frame loops below (opaque, so it is not
+  // rebuilt per frame)
+  f32x4 seed = {-kOff, -kOff, -kOff, -kOff};
+  asm volatile("" : "+v"(seed));
   int* seq = reinterpret_cast<int*>(c.sRed + 2 * kRB);   // 2 partial buffers, seq words, row max
   // the first chunk's staging ahead of the chunk loop (see scene_producer);
   // the recurrence waves load h and form its softmax numerators meanwhile
@@ -835,7 +840,7 @@ __device__ __forceinline__ void scene_recurrence(const StepArgs& a, const SceneL
         int fln;
         float4 bn;
         rc.step_seq(b, z, c.sRed + ((g + 1) & 1) * kRB, seq, g + 3, c.wv, c.q, c.L, c.sFlag, as_lane,
-                    fln, bn, g + 1 == c.nf);
+                    fln, bn, seed, g + 1 == c.nf);
       }
       __builtin_amdgcn_s_setprio(0);
     } else if (live) {
@@ -853,7 +858,7 @@ __device__ __forceinline__ void scene_recurrence(const StepArgs& a, const SceneL
           wait_as(c.sFlag + fl, g + 1, as_lane + fl * kD * kD, b);
         const int fn = fl + 1 < cnt ? fl + 1 : fl;   // next frame's ring slot (itself at the end)
         rc.step_seq(b, z, c.sRed + ((g + 1) & 1) * kRB, seq, g + 3, c.wv, c.q, c.L, c.sFlag + fn,
-                    as_lane + fn * kD * kD, fln, bn, g + 1 == c.nf);
+                    as_lane + fn * kD * kD, fln, bn, seed, g + 1 == c.nf);
       };
       float4 b0, b1;
       int f0 = read_as(c.sFlag, as_lane, b0), f1 = 0;
@@ -986,7 +991,9 @@ __device__ __forceinline__ void pred_tile(const float* M, const float* sWo, floa
     // floats 4q..4q+3 and 16+4q..16+4q+3 (r = 2 step + xy), so two 16-byte
     // stores at the offsets of its two target loads; pedestrians >= n_active
     // are not written (a contiguous n_active * 96-byte run per frame)
-    const int off = n * kL2 * 4;
+    // (n * 96 as the lane's L * 96, a loop constant, plus the tile's scalar
+    // 16 t * 96: no integer multiply per item)
+    const int off = L * (kL2 * 4) + t * (16 * kL2 * 4);
     if constexpr (REP) {
       for (int r = 0; r < nrep; ++r) {
         const int fo = r * (kL2 * Nmax * 4);
@@ -1066,7 +1073,10 @@ __device__ __forceinline__ void pred_tile(const float* M, const float* sWo, floa
   const float tt = __uint_as_float(p3[0]) + __uint_as_float(p3[1]);   // rows: ea, ec, eb, ec
   const auto p4 = sw16(tt, tt);                                       // [0]: rows ea, ea, eb, eb
   const auto p5 = sw32(__uint_as_float(p4[0]), __uint_as_float(p4[0]));   // [1]: eb everywhere
-  const float sa = __uint_as_float(p4[0]), sb = __uint_as_float(p5[1]), sc = tt;   // row 1
+  // row 1 (the only row whose terms are kept, g1): p5[0] there is p4[0] (ea)
+  // and p4[1] is tt (ec), so neither swap's input outlives it — no copy of
+  // tt or p4[0] in front of the swaps
+  const float sa = __uint_as_float(p5[0]), sb = __uint_as_float(p5[1]), sc = __uint_as_float(p4[1]);
   {
     const float g1 = (has_t && q == 1) ? wrep : 0.f;   // group 1's lanes of pedestrians with targets
     const float fx = d1[2], fy = d1[3];
@@ -1415,7 +1425,8 @@ __device__ __forceinline__ void load_targets(brsrc tgr, int Nmax, int nact, int 
                                              bool ok, int L, int q, float2 (&tg)[4], int tfb) {
   const int ne = 16 * t + L;
   ok = ok && ne < nact;
-  const int base = (fb + fl) * tfb + (ne < Nmax ? ne : 0) * (kL2 * 4);
+  // (ne * 96 = the lane's L * 96, a loop constant, + the tile's scalar 16 t * 96)
+  const int base = (fb + fl) * tfb + (ne < Nmax ? L * (kL2 * 4) + t * (16 * kL2 * 4) : 0);
   // two 16-B loads (rows are 96 B: every float4 is 16-B aligned)
   const float4 u = bload4(tgr, ok ? base + 16 * q : kBufOff);
   const float4 w = bload4(tgr, ok && q < 2 ? base + 64 + 16 * q : kBufOff);
