@@ -94,13 +94,21 @@
  * place of chol, over the same joint samples: the scene-level rank calibration
  * is the figure that says whether the coupling is too weak or too strong.
  *
+ * g2k_coupled_scene_modes_f32: the arguments, outputs, checks and workspace
+ * query of g2k_fullcov_scene_modes_f32 (include/g2k_scene_modes.h;
+ * g2k_scene_modes_workspace_bytes is one size for every head) with cpl in
+ * place of chol, over the same joint samples: the k-medoid reduction of the K
+ * joint draws to M scene modes, where a shared part lets a few draws cover a
+ * scene whose pedestrians move together.
+ *
  * Alignment (bytes).  g2k_coupled_stats_f32: targets 8, whiten 8, within 8,
  * between 8, counts 8, stats 8, workspace 8.  g2k_coupled_sample_f32: pred 4,
  * cpl 4, out 4.  g2k_coupled_joint_eval_f32: targets 8, sums_i 8, workspace 4.
  * g2k_coupled_couple_scores_f32: targets 8, per_couple 4, per_frame_f 4,
  * per_frame_i 4, sums 4, hist 4, tot 8, workspace 4.
  * g2k_coupled_scene_ranks_f32: targets 8, per_frame_i 4, per_frame_d 8, sums 8,
- * hist 4, tot 8, workspace 8.
+ * hist 4, tot 8, workspace 8.  g2k_coupled_scene_modes_f32: targets 8,
+ * per_frame_i 4, per_frame_d 8, medoids 4, counts 4, sums 8, tot 8, workspace 8.
  */
 #ifndef G2K_COUPLED_H_
 #define G2K_COUPLED_H_
@@ -141,6 +149,12 @@ int g2k_coupled_scene_ranks_f32(const g2k_dims* d, const float* pred, const floa
                                 int32_t B, int32_t* per_frame_i, double* per_frame_d, double* sums,
                                 int32_t* hist, int64_t* tot, void* workspace, int64_t workspace_bytes,
                                 void* stream);
+int g2k_coupled_scene_modes_f32(const g2k_dims* d, const float* pred, const float* targets,
+                                const int32_t* n_active, const int32_t* n_frames,
+                                const uint8_t* ped_mask, const float* cpl, uint64_t seed, int32_t K,
+                                int32_t M, int32_t iters, float miss_radius, int32_t* per_frame_i,
+                                double* per_frame_d, int32_t* medoids, int32_t* counts, double* sums,
+                                int64_t* tot, void* workspace, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -6,7 +6,8 @@ the build's own: --data_root (Q8), --device, --mode,
 --calibration, --fullcov_head, --mixture_head, --mixture_components,
 --mixture_iters, --coupled_head, --kde_nll, --kde_floor, --sample_scores, --sample_ranks,
 --rank_bins, --sample_kinematics, --kin_bins, --couple_scores, --couple_bins,
---couple_reach, --scene_ranks, --scene_bins, --sample_modes, --modes_draws, --modes_iters, --miss_radius."""
+--couple_reach, --scene_ranks, --scene_bins, --scene_modes,
+--scene_modes_iters, --sample_modes, --modes_draws, --modes_iters, --miss_radius."""
 import argparse
 
 
@@ -160,6 +161,16 @@ class ArgsParser:
     parser.add_argument('--scene_bins', type=int, default=0,
                         help='--scene_ranks: bins of the rank histograms, a divisor of K + 1 up to 64 '
                              '(0: the largest divisor <= 32)')
+    parser.add_argument('--scene_modes', type=int, default=0,
+                        help='--num_samples K (max(M, 2) <= K <= 64): M in 1..32 also reduces the K draws '
+                             'taken as joint samples of a scene to M scene modes, each one of the draws '
+                             'with a probability (k-medoids in double precision), and reports '
+                             'minJADE_M / minJFDE_M of the modes, their Brier variants, the scene-level '
+                             'miss rate at --miss_radius, the clustering cost and the minJADE of the '
+                             'first M raw draws and of all K, of the per-step head and, with '
+                             '--fullcov_head / --mixture_head / --coupled_head, of those heads (0: off)')
+    parser.add_argument('--scene_modes_iters', type=int, default=10,
+                        help='--scene_modes: alternating rounds after the start, at most, 0..32')
     parser.add_argument('--sample_modes', type=int, default=0,
                         help='--num_samples: M in 1..32 also reduces --modes_draws draws of each head '
                              'in use to M representative trajectories with probabilities (k-means '

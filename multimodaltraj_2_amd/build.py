@@ -24,6 +24,7 @@ HDR = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(ROOT, "includ
                                                       os.path.join(ROOT, "include", "g2k_couples.h"),
                                                       os.path.join(ROOT, "include", "g2k_coupled.h"),
                                                       os.path.join(ROOT, "include", "g2k_scene_ranks.h"),
+                                                      os.path.join(ROOT, "include", "g2k_scene_modes.h"),
                                                       os.path.join(ROOT, "include", "g2k_step_fixed.h")]
 OUT = os.path.join(HERE, "libg2k_hip.so")
 OBJ = os.path.join(HERE, "build")

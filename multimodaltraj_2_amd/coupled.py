@@ -16,8 +16,8 @@ NLL of the independent head with the same marginals: their difference is what
 the coupling is worth in nats.  ``fit`` is the closed-form method-of-moments
 estimate (one stats launch, then a 24 x 24 projection in float64 on the host),
 ``sample`` draws one reproducible joint trajectory set, and ``joint_eval`` /
-``couple_scores`` / ``scene_ranks`` are nll.SampledEvals' over this head's joint
-draws, one call each.  The per-pedestrian evaluations belong to ``marginal()``.
+``couple_scores`` / ``scene_ranks`` / ``scene_modes`` are nll.SampledEvals' over
+this head's joint draws, one call each.  The per-pedestrian evaluations belong to ``marginal()``.
 
 The entry points were added after ABI 11 and are declared in a header of their
 own, so this module binds them itself on the handle ``_lib.load()`` returns
@@ -31,7 +31,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib, couples, sceneranks
+from . import _lib, couples, scenemodes, sceneranks
 from .frame_step import PRED_LEN, _check_dev, _ptr, _stream
 from .nll import SampledEvals, _check_pairs_inputs
 
@@ -53,6 +53,7 @@ SYMBOLS = {
                                           _vp, _vp, _vp, _vp, _i64, _vp]),
     "g2k_coupled_couple_scores_f32": couples._CPL,
     "g2k_coupled_scene_ranks_f32": sceneranks._SCN,
+    "g2k_coupled_scene_modes_f32": scenemodes._SMD,
 }
 
 
@@ -191,10 +192,11 @@ class CoupledStats:
 
 
 class CoupledHead(SampledEvals):
-    """The scene-coupled head.  Of nll.SampledEvals it has the three
+    """The scene-coupled head.  Of nll.SampledEvals it has the four
     evaluations of JOINT draws, ``joint_eval`` (g2k_coupled_joint_eval_f32),
-    ``couple_scores`` (g2k_coupled_couple_scores_f32) and ``scene_ranks``
-    (g2k_coupled_scene_ranks_f32), GPU tensors only; the per-pedestrian ones
+    ``couple_scores`` (g2k_coupled_couple_scores_f32), ``scene_ranks``
+    (g2k_coupled_scene_ranks_f32) and ``scene_modes``
+    (g2k_coupled_scene_modes_f32), GPU tensors only; the per-pedestrian ones
     raise: they are ``marginal()``'s."""
     _PREFIX = "g2k_coupled_"
     _JOINT_GPU_ONLY = True

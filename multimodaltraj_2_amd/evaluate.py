@@ -96,7 +96,14 @@ g2k_scene_ranks_f32 call per head in use (csrc/g2k_scene_ranks.hip;
 SCN_FIGURES): the targets' whole configuration of a scene ranked among the
 draws' by typicality, common mode and within-scene spread in --scene_bins bins,
 and the fair energy score of the scene's joint law, which is reported and never
-gated on (it hardly sees dependence).  --coupled_head train / eval
+gated on (it hardly sees dependence).  --scene_modes M (1 <= M <= 32, max(M, 2)
+<= K <= 64) reduces the same joint draws of every scene to M scene modes, each
+one of the draws with a probability, one g2k_scene_modes_f32 call per head in
+use (csrc/g2k_scene_modes.hip: k-medoids in double precision,
+--scene_modes_iters rounds; SMD_FIGURES): minJADE_M / minJFDE_M of the modes,
+their Brier variants, the scene-level miss rate at --miss_radius, the
+clustering cost, and the minJADE of the first M raw draws and of all K.
+--coupled_head train / eval
 fits the one head that MODELS that dependence (coupled.CoupledHead,
 csrc/g2k_coupled.hip: r = c + e, c shared by the members of a scene-frame;
 closed form) and reports the shared part of the residual variance, its exact
@@ -158,6 +165,11 @@ SCN_FIGURES = (("scn_frames", "scn_es") + tuple(f"scn_{f}_{g}" for g in SCN_FEAT
 FULLCOV_SCN_FIGURES = tuple("fullcov_" + k for k in SCN_FIGURES)
 MIX_SCN_FIGURES = tuple("mix_" + k for k in SCN_FIGURES)
 COUPLED_SCN_FIGURES = tuple("coupled_" + k for k in SCN_FIGURES)
+SMD_FIGURES = ("smd_frames", "smd_jade", "smd_jfde", "smd_brier_jade", "smd_brier_jfde", "smd_miss", "smd_cost",
+               "smd_raw_jade", "smd_all_jade", "smd_rounds")
+FULLCOV_SMD_FIGURES = tuple("fullcov_" + k for k in SMD_FIGURES)
+MIX_SMD_FIGURES = tuple("mix_" + k for k in SMD_FIGURES)
+COUPLED_SMD_FIGURES = tuple("coupled_" + k for k in SMD_FIGURES)
 COUPLED_FIGURES = ("coupled_share", "coupled_nll", "coupled_nll_gain", "coupled_q_within", "coupled_q_between",
                    "coupled_clipped")
 COUPLED_JOINT_FIGURES = ("coupled_jade", "coupled_jfde", "coupled_collision_rate",
@@ -332,6 +344,26 @@ def _scene_line(name, sr, dataset, res, prefix=""):
             + ", ".join(parts))
 
 
+def scene_mode_figures(sm, prefix=""):
+    """SMD_FIGURES (``prefix`` "fullcov_", "mix_", "coupled_": those heads') of
+    a scenemodes.SceneModes."""
+    fig = {"smd_frames": sm.frames, "smd_jade": sm.jade, "smd_jfde": sm.jfde, "smd_brier_jade": sm.brier_jade,
+           "smd_brier_jfde": sm.brier_jfde, "smd_miss": sm.miss_rate, "smd_cost": sm.cost,
+           "smd_raw_jade": sm.raw_jade, "smd_all_jade": sm.all_jade, "smd_rounds": sm.rounds}
+    return {prefix + k: fig[k] for k in SMD_FIGURES}
+
+
+def _scene_mode_line(name, sm, dataset, res, prefix=""):
+    """The log line of one head's SMD_FIGURES."""
+    v = {k: res[prefix + k] for k in SMD_FIGURES}
+    return (f"{name} of the {sm.k} joint draws on dataset {dataset}: {v['smd_frames']} scenes reduced to "
+            f"{sm.modes} modes in {v['smd_rounds']:.3g} rounds of at most {sm.iters}, minJADE_{sm.modes} "
+            f"{v['smd_jade']:.6g} minJFDE_{sm.modes} {v['smd_jfde']:.6g} (the first {sm.modes} raw draws "
+            f"{v['smd_raw_jade']:.6g}, all {sm.k} draws {v['smd_all_jade']:.6g}), Brier "
+            f"{v['smd_brier_jade']:.6g} / {v['smd_brier_jfde']:.6g}, cost {v['smd_cost']:.6g}, scene miss "
+            f"rate at {sm.miss_radius:g} {v['smd_miss']:.4f}")
+
+
 def _couple_line(name, cs, dataset, res, prefix=""):
     """The log line of one head's CPL_FIGURES."""
     parts = [f"{g} crps {res[prefix + 'cpl_crps_' + g]:.4f} pit {res[prefix + 'cpl_pit_' + g]:.4f} "
@@ -451,6 +483,12 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
     ``scene_ranks`` call per head in use (csrc/g2k_scene_ranks.hip), the
     other heads' prefixed "fullcov_" / "mix_" / "coupled_", a log line each
     (``keep["scene_ranks"]``, ``keep[<head>]["scene_ranks"]``).
+    --scene_modes M (1..32; max(M, 2) <= K <= 64; --scene_modes_iters,
+    --miss_radius) adds SMD_FIGURES directly after the same head's
+    scene-rank figures, from one ``scene_modes`` call per head in use
+    (csrc/g2k_scene_modes.hip), the other heads' prefixed "fullcov_" / "mix_"
+    / "coupled_", a log line each (``keep["scene_modes"]``,
+    ``keep[<head>]["scene_modes"]``).
     --coupled_head train / eval then fits the scene-coupled head
     (coupled.CoupledHead, csrc/g2k_coupled.hip: closed form) on the same
     scenes as --fullcov_head's modes and adds COUPLED_FIGURES from one stats
@@ -517,6 +555,21 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
             raise ValueError(f"--scene_bins must be 0 (automatic) or a divisor of K + 1 = {K + 1} in "
                              f"1..{sn.BMAX}") from None
         scn_kw = dict(seed=args.sample_seed, want_per_frame=keep is not None)
+    n_smd = int(getattr(args, "scene_modes", 0) or 0)
+    if n_smd:
+        from . import scenemodes as sd
+        if not 1 <= n_smd <= sd.MMAX:
+            raise ValueError("--scene_modes M: 0 (off) or 1 <= M <= 32")
+        if not max(n_smd, sd.KMIN) <= K <= sd.KMAX:
+            raise ValueError("--scene_modes M needs --num_samples K with max(M, 2) <= K <= 64")
+        smd_iters = int(getattr(args, "scene_modes_iters", 10))
+        if not 0 <= smd_iters <= sd.ITERS_MAX:
+            raise ValueError("--scene_modes_iters must be in 0..32")
+        smd_radius = float(getattr(args, "miss_radius", 0.0) or 0.0)
+        if not (np.isfinite(smd_radius) and smd_radius >= 0):
+            raise ValueError("--miss_radius must be finite and >= 0")
+        smd_kw = dict(iters=smd_iters, miss_radius=smd_radius, seed=args.sample_seed,
+                      want_per_frame=keep is not None, want_modes=keep is not None)
     n_modes = int(getattr(args, "sample_modes", 0) or 0)
     if n_modes:
         if not 1 <= n_modes <= 32:
@@ -630,8 +683,14 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                              ped_mask=t["ped_mask"], **scn_kw)
         res.update(scene_figures(scn))
         log(_scene_line("scene ranks", scn, args.leaveDataset, res))
+    smd = None
+    if n_smd:
+        smd = gh.scene_modes(out.pred, t["targets"], t["n_active"], K, n_smd, n_frames=one,
+                             ped_mask=t["ped_mask"], **smd_kw)
+        res.update(scene_mode_figures(smd))
+        log(_scene_mode_line("scene modes", smd, args.leaveDataset, res))
     fc_mode = getattr(args, "fullcov_head", "off") or "off"
-    fc = fc_st = fc_bk = fc_joint = fc_kde = fc_scores = fc_modes = fc_ranks = fc_kin = fc_cpl = fc_scn = None
+    fc = fc_st = fc_bk = fc_joint = fc_kde = fc_scores = fc_modes = fc_ranks = fc_kin = fc_cpl = fc_scn = fc_smd = None
     if fc_mode != "off":
         from .fullcov import FullCovHead
         fc = FullCovHead(device=device)
@@ -709,8 +768,13 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                                     ped_mask=t["ped_mask"], **scn_kw)
             res.update(scene_figures(fc_scn, "fullcov_"))
             log(_scene_line("full-covariance scene ranks", fc_scn, args.leaveDataset, res, "fullcov_"))
+        if n_smd:
+            fc_smd = fc.scene_modes(out.pred, t["targets"], t["n_active"], K, n_smd, n_frames=one,
+                                    ped_mask=t["ped_mask"], **smd_kw)
+            res.update(scene_mode_figures(fc_smd, "fullcov_"))
+            log(_scene_mode_line("full-covariance scene modes", fc_smd, args.leaveDataset, res, "fullcov_"))
     mx_mode = getattr(args, "mixture_head", "off") or "off"
-    mx = mx_fit = mx_st = mx_bk = mx_joint = mx_kde = mx_scores = mx_modes = mx_ranks = mx_kin = mx_cpl = mx_scn = None
+    mx = mx_fit = mx_st = mx_bk = mx_joint = mx_kde = mx_scores = mx_modes = mx_ranks = mx_kin = mx_cpl = mx_scn = mx_smd = None
     if mx_mode != "off":
         from .mixture import MixtureHead
         mx = MixtureHead(components=int(getattr(args, "mixture_components", 3)), device=device)
@@ -788,8 +852,13 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                                     ped_mask=t["ped_mask"], **scn_kw)
             res.update(scene_figures(mx_scn, "mix_"))
             log(_scene_line("mixture scene ranks", mx_scn, args.leaveDataset, res, "mix_"))
+        if n_smd:
+            mx_smd = mx.scene_modes(out.pred, t["targets"], t["n_active"], K, n_smd, n_frames=one,
+                                    ped_mask=t["ped_mask"], **smd_kw)
+            res.update(scene_mode_figures(mx_smd, "mix_"))
+            log(_scene_mode_line("mixture scene modes", mx_smd, args.leaveDataset, res, "mix_"))
     co_mode = getattr(args, "coupled_head", "off") or "off"
-    co = co_fit = co_st = co_joint = co_cpl = co_scn = None
+    co = co_fit = co_st = co_joint = co_cpl = co_scn = co_smd = None
     if co_mode != "off":
         from .coupled import CoupledHead
         co = CoupledHead(device=device)
@@ -831,6 +900,11 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                                     ped_mask=t["ped_mask"], **scn_kw)
             res.update(scene_figures(co_scn, "coupled_"))
             log(_scene_line("coupled scene ranks", co_scn, args.leaveDataset, res, "coupled_"))
+        if n_smd:
+            co_smd = co.scene_modes(out.pred, t["targets"], t["n_active"], K, n_smd, n_frames=one,
+                                    ped_mask=t["ped_mask"], **smd_kw)
+            res.update(scene_mode_figures(co_smd, "coupled_"))
+            log(_scene_mode_line("coupled scene modes", co_smd, args.leaveDataset, res, "coupled_"))
     if keep is not None:
         if co is not None:
             keep.update(coupled=dict(head=co, fit=co_fit, stats=co_st))
@@ -840,6 +914,8 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                 keep["coupled"]["couples"] = co_cpl
             if co_scn is not None:
                 keep["coupled"]["scene_ranks"] = co_scn
+            if co_smd is not None:
+                keep["coupled"]["scene_modes"] = co_smd
         keep.update(plan=plan, pred=out.pred, head=gh.head, out=bk, n_frames=np.ones(S, np.int32),
                     joint=joint)
         if mx is not None:
@@ -860,6 +936,8 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                 keep["mixture"]["couples"] = mx_cpl
             if mx_scn is not None:
                 keep["mixture"]["scene_ranks"] = mx_scn
+            if mx_smd is not None:
+                keep["mixture"]["scene_modes"] = mx_smd
         if calibrate:
             keep.update(calib=calib, fitted=fitted)
         if kde is not None:
@@ -876,6 +954,8 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
             keep.update(couples=cpl)
         if scn is not None:
             keep.update(scene_ranks=scn)
+        if smd is not None:
+            keep.update(scene_modes=smd)
         if fc is not None:
             keep.update(fullcov=dict(stats=fc_st, out=fc_bk, fitted=ffit), fullcov_chol=fc.chol)
             if fc_joint is not None:
@@ -894,6 +974,8 @@ def evaluate_best_of_k(args, params, device, log=print, keep=None):
                 keep["fullcov"]["couples"] = fc_cpl
             if fc_scn is not None:
                 keep["fullcov"]["scene_ranks"] = fc_scn
+            if fc_smd is not None:
+                keep["fullcov"]["scene_modes"] = fc_smd
     return res
 
 

@@ -326,9 +326,9 @@ def _launch(lib, symbol, d, pred, targets, n_active, n_frames, ped_mask, head, s
 
 
 class SampledEvals:
-    """The nine sampled evaluations of a probabilistic head, once for the
+    """The ten sampled evaluations of a probabilistic head, once for the
     heads (GaussianHead below, fullcov.FullCovHead, mixture.MixtureHead;
-    coupled.CoupledHead takes the three of JOINT draws): each
+    coupled.CoupledHead takes the four of JOINT draws): each
     is ONE launch over the K draws ``sample(pred, seed + i)``, i < k, of the
     head it is called on, none of them stored.  A head supplies ``_PREFIX``
     (its entry points are ``_PREFIX`` + best_of_k_f32, ...), ``_head_tensor``
@@ -513,6 +513,21 @@ class SampledEvals:
         d, head = self._sampled_inputs(pred, targets, n_active, n_frames, ped_mask, targets_shared)
         return _scene_ranks(self._PREFIX + "scene_ranks_f32", head, d, pred, targets, n_active, k, bins,
                             seed, n_frames, ped_mask, want_per_frame, stream)
+
+    def scene_modes(self, pred, targets, n_active, k, m, iters=10, miss_radius=0.0, seed=0, *, n_frames=None,
+                    ped_mask=None, targets_shared=False, want_per_frame=False, want_modes=True, stream=None):
+        """K-medoid reduction of the K JOINT draws ``sample(pred, seed + i)``,
+        i < k, of every scene-frame to ``m`` scene modes, each one of the draws
+        (named by its index) with a probability, and the modes' scores, in one
+        call (``_PREFIX`` + scene_modes_f32, csrc/g2k_scene_modes.hip):
+        minJADE_M / minJFDE_M, their Brier variants, the scene-level miss rate
+        at ``miss_radius``, the clustering cost, and the minJADE of the first m
+        raw draws and of all k -> scenemodes.SceneModes.  GPU tensors only.  m
+        in 1..32, k in max(m, 2)..64, iters in 0..32."""
+        from .scenemodes import _scene_modes
+        d, head = self._sampled_inputs(pred, targets, n_active, n_frames, ped_mask, targets_shared)
+        return _scene_modes(self._PREFIX + "scene_modes_f32", head, d, pred, targets, n_active, k, m, iters,
+                            miss_radius, seed, n_frames, ped_mask, want_per_frame, want_modes, stream)
 
 
 class GaussianHead(SampledEvals):

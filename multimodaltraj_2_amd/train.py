@@ -60,7 +60,9 @@
   draws in --couple_bins bins within --couple_reach, one g2k_couple_scores_f32
   call per head in use; with --scene_ranks 1 also the scene-level rank
   calibration of the K joint draws in --scene_bins bins, one
-  g2k_scene_ranks_f32 call per head in use).
+  g2k_scene_ranks_f32 call per head in use; with --scene_modes M also the
+  k-medoid reduction of the K joint draws to M scene modes in
+  --scene_modes_iters rounds, one g2k_scene_modes_f32 call per head in use).
 
 The model weights are one seeded N(0, 1) draw (quirk Q15: the reference
 re-draws them every batch), padded to Nmax (8 for the node slice).
