@@ -10,6 +10,18 @@ from oracle import g2k_ref as ref
 
 L = 12
 MASK64 = (1 << 64) - 1
+# The seeds at which draw 1's 64-bit seed, which the kernels form in 32-bit halves (lo = seed_lo + k, hi =
+# seed_hi + (lo < seed_lo)), carries out of the low word: A's draw 0 has the low word all ones and draw 1
+# is 2^32; W's draw 1 wraps to seed 0.
+SEED_A, SEED_W = (1 << 32) - 1, MASK64
+BOUNDARY_SEEDS = {"A": SEED_A, "W": SEED_W}
+
+
+def draw_seed(seed, k, carry=True):
+    """Draw k's seed, (seed + k) mod 2^64; ``carry=False``: what a kernel that
+    dropped the carry would use — the high word left at seed >> 32."""
+    s = (int(seed) + k) & MASK64
+    return s if carry else ((int(seed) & MASK64) >> 32 << 32) | (s & 0xFFFFFFFF)
 
 
 def pair_mask(S, F, N, n_active, n_frames=None, ped_mask=None):

@@ -17,7 +17,7 @@ import numpy as np
 
 from tests import fullcov_ref
 from tests import mix_eval_ref as me
-from tests.bestk_ref import pair_mask
+from tests.bestk_ref import draw_seed, pair_mask
 from tests.ranks_cases import HEADS, SEED, sampler, scaled   # noqa: F401 (re-exported)
 
 L = 12
@@ -102,13 +102,15 @@ def passes_of(i):
 
 
 @functools.lru_cache(maxsize=None)
-def oracle_draws(i, which):
+def oracle_draws(i, which, seed=None, carry=True):
     """[K, S, F, 24, N] float32: the checkers' restatement of the sampler's
-    draws for seeds seed + k, rounded to the sampler's fp32."""
+    draws for seeds seed + k (``seed`` None: the case's own), rounded to the
+    sampler's fp32; ``carry=False``: tests/bestk_ref.draw_seed's."""
     c = inputs(i)
     draw = sampler(which, c)
+    seed = c["seed"] if seed is None else seed
     with np.errstate(invalid="ignore"):
-        d = [draw(c["pred"], c["seed"] + k) for k in range(c["K"])]
+        d = [draw(c["pred"], draw_seed(seed, k, carry)) for k in range(c["K"])]
     return np.stack(d).astype(np.float32)
 
 

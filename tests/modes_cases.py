@@ -18,7 +18,7 @@ from oracle import g2k_ref as ref
 from tests import fullcov_ref
 from tests import mix_eval_ref as me
 from tests import mixture_ref as mr
-from tests.bestk_ref import MASK64, pair_mask
+from tests.bestk_ref import draw_seed, pair_mask
 
 L = 12
 SEED = (11 << 32) + 977
@@ -59,6 +59,10 @@ CASES = [
     ("collapsed", 1, 2, 8,   16,  4,  3,  [6],         None,      False, False, dict(g=16, fc=2, c=1), 1),
 ]
 IDS = [c[0] for c in CASES]
+# The row run at the boundary seed A (tests/bestk_ref.py: draw 1's seed carries out of the low word).  The
+# smallest row, m1, has one centre: its integer outputs (mA = mF = 0, live = 1) are the same whatever the
+# draws, so they could not tell a dropped carry; the next-smallest, mk, is taken for every head.
+BOUNDARY_ROW = "mk"
 
 
 def heads_of(i):
@@ -126,20 +130,21 @@ def passes_of(i):
 
 
 @functools.lru_cache(maxsize=None)
-def oracle_draws(i, which):
+def oracle_draws(i, which, seed=None, carry=True):
     """[K, S, F, 24, N] float32: the checkers' restatement of the sampler's
     draws for seeds seed + k (oracle/g2k_ref.py gauss_sample, tests/
-    fullcov_ref.py sample, tests/mixture_ref.py sample), rounded to the
-    sampler's fp32."""
+    fullcov_ref.py sample, tests/mixture_ref.py sample; ``seed`` None: the
+    case's own), rounded to the sampler's fp32; ``carry=False``:
+    tests/bestk_ref.draw_seed's."""
     c = inputs(i)
+    seeds = [draw_seed(c["seed"] if seed is None else seed, k, carry) for k in range(c["K"])]
     with np.errstate(invalid="ignore"):
         if which == "per_step":
-            d = [ref.gauss_sample(c["pred"], c["head"], (c["seed"] + k) & MASK64) for k in range(c["K"])]
+            d = [ref.gauss_sample(c["pred"], c["head"], s) for s in seeds]
         elif which == "fullcov":
-            d = [fullcov_ref.sample(c["pred"], c["chol"], (c["seed"] + k) & MASK64)
-                 for k in range(c["K"])]
+            d = [fullcov_ref.sample(c["pred"], c["chol"], s) for s in seeds]
         else:
-            d = [mr.sample(c["pred"], c["mix"], (c["seed"] + k) & MASK64)[0] for k in range(c["K"])]
+            d = [mr.sample(c["pred"], c["mix"], s)[0] for s in seeds]
     return np.stack(d).astype(np.float32)
 
 

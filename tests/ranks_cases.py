@@ -18,7 +18,7 @@ from oracle import g2k_ref as ref
 from tests import fullcov_ref
 from tests import mix_eval_ref as me
 from tests import mixture_ref as mr
-from tests.bestk_ref import MASK64, pair_mask
+from tests.bestk_ref import MASK64, draw_seed, pair_mask
 
 L = 12
 SEED = (11 << 32) + 8765
@@ -128,11 +128,13 @@ def scaled(which, c, by):
 
 
 @functools.lru_cache(maxsize=None)
-def oracle_draws(i, which):
+def oracle_draws(i, which, seed=None, carry=True):
     """[K, S, F, 24, N] float32: the checkers' restatement of the sampler's
-    draws for seeds seed + k, rounded to the sampler's fp32."""
+    draws for seeds seed + k (``seed`` None: the case's own), rounded to the
+    sampler's fp32; ``carry=False``: tests/bestk_ref.draw_seed's."""
     c = inputs(i)
     draw = sampler(which, c)
+    seed = c["seed"] if seed is None else seed
     with np.errstate(invalid="ignore"):
-        d = [draw(c["pred"], c["seed"] + k) for k in range(c["K"])]
+        d = [draw(c["pred"], draw_seed(seed, k, carry)) for k in range(c["K"])]
     return np.stack(d).astype(np.float32)

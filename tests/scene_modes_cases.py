@@ -66,10 +66,11 @@ def inputs(i):
     return dict(sc.inputs(base(i)), M=M, iters=iters, radius=RADIUS)
 
 
-def oracle_draws(i, which):
+def oracle_draws(i, which, seed=None, carry=True):
     """[K, S, F, 24, N] float32: the restated sampler's draws for seeds seed +
-    k (scene_ranks_cases': computed once for both families' tests)."""
-    return sc.oracle_draws(base(i), which)
+    k (scene_ranks_cases': computed once for both families' tests; ``seed`` and
+    ``carry`` as there)."""
+    return sc.oracle_draws(base(i), which, seed, carry)
 
 
 # ---------------------------------------------------------------------------

@@ -21,7 +21,7 @@ from tests import coupled_cases as cx
 from tests import coupled_ref
 from tests import fullcov_ref
 from tests import mix_eval_ref as me
-from tests.bestk_ref import MASK64, pair_mask
+from tests.bestk_ref import MASK64, draw_seed, pair_mask
 from tests.ranks_cases import SEED, sampler as _sampler
 
 L = 12
@@ -47,6 +47,12 @@ CASES = [
     ("k32",    1, 2, 24,  32, 11, [9],                        None,         False, 8),
 ]
 IDS = [c[0] for c in CASES]
+# The rows run at the boundary seeds (tests/bestk_ref.BOUNDARY_SEEDS: draw 1's seed carries out of the low
+# word), per (seed, head): k2, the smallest.  At W the coupled head's nine ranks of k2 (K = 2: each one of
+# 0, 1, 2) happen to be the same with the carry dropped, so the integer outputs could not tell; that
+# combination takes the next-smallest row, k20.
+BOUNDARY = [(at, w, "k20" if (at, w) == ("W", "coupled") else "k2") for at in ("A", "W") for w in HEADS]
+BOUNDARY_IDS = [f"{at}-{row}-{w}" for at, w, row in BOUNDARY]
 
 
 def geometry(N, K):
@@ -116,13 +122,15 @@ def sampler(which, c):
 
 
 @functools.lru_cache(maxsize=None)
-def oracle_draws(i, which):
+def oracle_draws(i, which, seed=None, carry=True):
     """[K, S, F, 24, N] float32: the restated sampler's draws for seeds seed +
-    k, rounded to the sampler's fp32."""
+    k (``seed`` None: the case's own), rounded to the sampler's fp32;
+    ``carry=False``: tests/bestk_ref.draw_seed's."""
     c = inputs(i)
     draw = sampler(which, c)
+    seed = c["seed"] if seed is None else seed
     with np.errstate(invalid="ignore"):
-        d = [draw(c["pred"], c["seed"] + k) for k in range(c["K"])]
+        d = [draw(c["pred"], draw_seed(seed, k, carry)) for k in range(c["K"])]
     return np.stack(d).astype(np.float32)
 
 

@@ -20,6 +20,7 @@ from multimodaltraj_2_amd import build as g2k_build
 from oracle import g2k_ref as ref
 from tests import couples_cases as cc
 from tests import couples_ref as cr
+from tests.bestk_ref import BOUNDARY_SEEDS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "g2k_couples.h")
@@ -335,6 +336,30 @@ def test_checker_against_plain_loops():
     assert qmin.dtype == np.float32
     for j in range(50):
         assert [float(qmin[j]), float(qfin[j])] == cr.features_loops(za[j], zb[j])
+
+
+def carry_check(draws_of, c, label):
+    """The boundary-seed rows' CPU side: on the restated draws (``draws_of(carry)``)
+    no fp32 tie between a draw and the target, and the checker's integer outputs
+    change when the draws are made with the carry dropped."""
+    R, D = (cr.couple_scores_ref(draws_of(carry), c["targets"], c["pred"], c["members"], c["K"], c["B"], c["reach"])
+            for carry in (True, False))
+    assert R["ties"] == 0 and D["ties"] == 0 and R["tot"][:, 0].sum() > 0
+    moved = np.abs(D["sums"] - R["sums"]).max()
+    print(f"{label}: carry dropped, sums move by {moved:.3g}, {int((D['per_couple'] != R['per_couple']).sum())} "
+          f"couples' ranks change")
+    assert not np.array_equal(D["per_couple"], R["per_couple"]) and not np.array_equal(D["hist"], R["hist"])
+    assert moved > 1e-2
+
+
+@pytest.mark.parametrize("which", cc.HEADS)
+@pytest.mark.parametrize("at", BOUNDARY_SEEDS)
+def test_boundary_seeds_have_no_ties_and_see_the_carry(at, which):
+    """Case k2 at the seeds whose low word carries at draw 1 (tests/bestk_ref.py;
+    tests/test_couple_scores_gpu.py runs the kernel there)."""
+    i = cc.IDS.index("k2")
+    carry_check(lambda carry: cc.oracle_draws(i, which, BOUNDARY_SEEDS[at], carry), cc.inputs(i),
+                f"k2 seed {at} {which}")
 
 
 def _band(xy):

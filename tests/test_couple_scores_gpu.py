@@ -18,7 +18,7 @@ import torch
 from tests import couples_cases as cc
 from tests import couples_ref as cr
 from tests.abi_arena import Arena, all_written
-from tests.bestk_ref import MASK64
+from tests.bestk_ref import BOUNDARY_SEEDS, MASK64
 from tests.scores_ref import TOL
 from tests.test_couple_scores import PROP, property_check, property_head, property_targets
 
@@ -69,11 +69,17 @@ def _reach(c):
     return None if np.isinf(c["reach"]) else c["reach"]
 
 
-def _run(i, which, dev, want_per_couple=True, want_per_frame=True, k=None, bins=None):
+def _key(i, which, seed):
+    """The caches' key: the case's own seed (None), or another."""
+    return (i, which) if seed is None else (i, which, seed)
+
+
+def _run(i, which, dev, want_per_couple=True, want_per_frame=True, k=None, bins=None, seed=None):
     c = cc.inputs(i)
     h, t = _device_inputs(i, which, dev)
-    r = h.couple_scores(t["pred"], t["targets"], t["n_active"], k or c["K"], bins or c["B"], seed=c["seed"],
-                        reach=_reach(c), n_frames=t["n_frames"], ped_mask=t["ped_mask"],
+    r = h.couple_scores(t["pred"], t["targets"], t["n_active"], k or c["K"], bins or c["B"],
+                        seed=c["seed"] if seed is None else seed, reach=_reach(c), n_frames=t["n_frames"],
+                        ped_mask=t["ped_mask"],
                         want_per_couple=want_per_couple, want_per_frame=want_per_frame,
                         targets_shared=c["shared"])
     torch.cuda.synchronize()
@@ -83,29 +89,33 @@ def _run(i, which, dev, want_per_couple=True, want_per_frame=True, k=None, bins=
 _RES, _DRAWS, _REF = {}, {}, {}
 
 
-def _result(i, which, dev):
-    if (i, which) not in _RES:
-        _RES[(i, which)] = _run(i, which, dev)
-    return _RES[(i, which)]
+def _result(i, which, dev, seed=None):
+    key = _key(i, which, seed)
+    if key not in _RES:
+        _RES[key] = _run(i, which, dev, seed=seed)
+    return _RES[key]
 
 
-def _draws(i, which, dev):
+def _draws(i, which, dev, seed=None):
     """The device's own K draws [K, S, F, 24, N] float32 (made once)."""
-    if (i, which) not in _DRAWS:
+    key = _key(i, which, seed)
+    if key not in _DRAWS:
         c = cc.inputs(i)
         h, t = _device_inputs(i, which, dev)
-        _DRAWS[(i, which)] = np.stack([h.sample(t["pred"], seed=(c["seed"] + k) & MASK64).cpu().numpy()
-                                       for k in range(c["K"])]).astype(np.float32)
-    return _DRAWS[(i, which)]
+        s0 = c["seed"] if seed is None else seed
+        _DRAWS[key] = np.stack([h.sample(t["pred"], seed=(s0 + k) & MASK64).cpu().numpy()
+                                for k in range(c["K"])]).astype(np.float32)
+    return _DRAWS[key]
 
 
-def _recount(i, which, dev):
+def _recount(i, which, dev, seed=None):
     """The checker over the device's own K draws (computed once)."""
-    if (i, which) not in _REF:
+    key = _key(i, which, seed)
+    if key not in _REF:
         c = cc.inputs(i)
-        _REF[(i, which)] = cr.couple_scores_ref(_draws(i, which, dev), c["targets"], c["pred"], c["members"],
-                                                c["K"], c["B"], c["reach"])
-    return _REF[(i, which)]
+        _REF[key] = cr.couple_scores_ref(_draws(i, which, dev, seed), c["targets"], c["pred"], c["members"],
+                                         c["K"], c["B"], c["reach"])
+    return _REF[key]
 
 
 def _check_against(r, R, label):
@@ -132,11 +142,10 @@ def _check_against(r, R, label):
     assert np.all(np.abs(sums - R["sums"]) <= TOL * ns * np.maximum(1.0, np.abs(R["sums"])))
 
 
-@pytest.mark.parametrize("i,which", ALL, ids=ALL_IDS)
-def test_ranks_equal_and_sums_within_tolerance(gpu, i, which):
+def _parity(dev, i, which, seed=None, label=""):
     c = cc.inputs(i)
-    r, R = _result(i, which, gpu), _recount(i, which, gpu)
-    _check_against(r, R, f"case {cc.IDS[i]} {which}")
+    r, R = _result(i, which, dev, seed), _recount(i, which, dev, seed)
+    _check_against(r, R, f"case {cc.IDS[i]} {which}{label}")
     if cc.IDS[i] == "none":
         assert r.couples == 0 and r.member_couples > 0 and np.isnan(r.crps("min"))
     if cc.IDS[i] in ("reach", "shared", "deal"):
@@ -151,6 +160,23 @@ def test_ranks_equal_and_sums_within_tolerance(gpu, i, which):
             assert (np.isnan(got) and np.isnan(exp)) or got == pytest.approx(exp, rel=1e-12, abs=1e-12), (g, name)
         if r.couples:
             assert 0.0 <= r.dev(g) <= 1.0 and 0.0 <= r.pit_mean(g) <= 1.0
+
+
+@pytest.mark.parametrize("i,which", ALL, ids=ALL_IDS)
+def test_ranks_equal_and_sums_within_tolerance(gpu, i, which):
+    _parity(gpu, i, which)
+
+
+@pytest.mark.parametrize("which", cc.HEADS)
+@pytest.mark.parametrize("at", BOUNDARY_SEEDS)
+def test_seed_whose_low_word_carries(gpu, at, which):
+    """Case k2 with the same assertions at the seeds where draw 1's seed carries
+    out of the low word (A = 2^32 - 1) and wraps to 0 (W = 2^64 - 1): the kernel's
+    own lo / hi arithmetic (csrc/g2k_couples.hip) against the samplers' at (seed +
+    k) mod 2^64.  tests/test_couple_scores.py: the checker's integer outputs
+    change when the carry is dropped.  The coupled head's:
+    tests/test_coupled_head_gpu.py."""
+    _parity(gpu, cc.IDS.index("k2"), which, BOUNDARY_SEEDS[at], f" seed {at}")
 
 
 def _raw_call(i, which, dev, pc, pf, pi, sums, hist, tot, t=None, ws=None, reach=None, dims=None):

@@ -24,6 +24,7 @@ from tests import couples_cases as cc
 from tests import couples_ref as cpr
 from tests import fullcov_ref as fr
 from tests import test_couple_scores as tcs
+from tests.bestk_ref import BOUNDARY_SEEDS, draw_seed
 from tests.test_couple_scores import DEV_FIN, DEV_MATCHED, DEV_MIN
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -463,6 +464,20 @@ def property_check(score, label=""):
     assert co["min"]["dev"] < DEV_MATCHED and co["fin"]["dev"] < DEV_MATCHED
     assert fc["fin"]["dev"] > DEV_FIN and fc["min"]["dev"] > DEV_MIN
     assert co["fin"]["crps"] < fc["fin"]["crps"]
+
+
+@pytest.mark.parametrize("at", BOUNDARY_SEEDS)
+def test_couple_scores_boundary_seeds_have_no_ties_and_see_the_carry(at):
+    """Case k2 with the scene-coupled head at the seeds whose low word carries at
+    draw 1 (tests/test_coupled_head_gpu.py runs g2k_coupled_couple_scores_f32
+    there)."""
+    c = cx.inputs(cx.IDS.index("k2"))
+
+    def draws_of(carry):
+        with np.errstate(invalid="ignore"):
+            return np.stack([cr.sample(c["pred"], c["cpl"], draw_seed(BOUNDARY_SEEDS[at], k, carry))
+                             for k in range(c["K"])]).astype(np.float32)
+    tcs.carry_check(draws_of, c, f"k2 seed {at} coupled")
 
 
 def test_coupled_targets_are_matched_by_the_coupled_head():

@@ -25,7 +25,7 @@ from tests import fullcov_joint_ref as fj
 from tests import fullcov_ref as fr
 from tests import test_fullcov_joint_gpu as tj
 from tests.abi_arena import Arena, all_written
-from tests.bestk_ref import MASK64, draw_errors
+from tests.bestk_ref import BOUNDARY_SEEDS, MASK64, draw_errors
 from tests.conftest import close
 from tests.scores_ref import TOL as CPL_TOL
 from tests.test_coupled_head import PROP, property_check, property_pred, property_targets
@@ -300,9 +300,10 @@ def _cpl_case(name, dev):
     return _CP[name]
 
 
-def _cpl_run(name, dev, head=None, k=None, bins=None, **kw):
+def _cpl_run(name, dev, head=None, k=None, bins=None, seed=None, **kw):
     c, h, t = _cpl_case(name, dev)
-    r = (head or h).couple_scores(t["pred"], t["targets"], t["n_active"], k or c["K"], bins or c["B"], seed=c["seed"],
+    r = (head or h).couple_scores(t["pred"], t["targets"], t["n_active"], k or c["K"], bins or c["B"],
+                                  seed=c["seed"] if seed is None else seed,
                                   reach=None if np.isinf(c["reach"]) else c["reach"], n_frames=t["n_frames"],
                                   ped_mask=t["ped_mask"], targets_shared=c["shared"],
                                   **dict(dict(want_per_couple=True, want_per_frame=True), **kw))
@@ -310,29 +311,46 @@ def _cpl_run(name, dev, head=None, k=None, bins=None, **kw):
     return r
 
 
-def _cpl_draws(name, dev):
+def _cpl_draws(name, dev, seed=None):
     """The device's own K joint draws [K, S, F, 24, N] float32 (made once)."""
-    if name not in _DRAWS:
+    key = name if seed is None else (name, seed)
+    if key not in _DRAWS:
         c, h, t = _cpl_case(name, dev)
-        _DRAWS[name] = np.stack([h.sample(t["pred"], seed=(c["seed"] + k) & MASK64).cpu().numpy()
-                                 for k in range(c["K"])]).astype(np.float32)
-    return _DRAWS[name]
+        s0 = c["seed"] if seed is None else seed
+        _DRAWS[key] = np.stack([h.sample(t["pred"], seed=(s0 + k) & MASK64).cpu().numpy()
+                                for k in range(c["K"])]).astype(np.float32)
+    return _DRAWS[key]
+
+
+def _cpl_parity(dev, name, seed=None, label=""):
+    c, h, t = _cpl_case(name, dev)
+    r = _cpl_run(name, dev, seed=seed)
+    R = cpr.couple_scores_ref(_cpl_draws(name, dev, seed), c["targets"], c["pred"], c["members"], c["K"], c["B"],
+                              c["reach"])
+    _check_against(r, R, f"coupled, case {name}{label}")
+    assert CPL_TOL <= 1e-4
+    again = _cpl_run(name, dev, seed=seed)
+    assert torch.equal(again.per_couple, r.per_couple) and _same(again.per_frame_f, r.per_frame_f)
+    assert _same(again.sums, r.sums) and torch.equal(again.hist, r.hist) and torch.equal(again.tot, r.tot)
+    no = _cpl_run(name, dev, seed=seed, want_per_couple=False, want_per_frame=False)
+    assert no.per_couple is None and _same(no.sums, r.sums) and torch.equal(no.hist, r.hist)
 
 
 @pytest.mark.parametrize("name", CPL)
 def test_couple_scores_against_the_devices_own_draws(gpu, name):
     """per_couple, per_frame_i, hist and tot EQUAL to the float32 restatement,
     the fp32 sums within scores_ref.TOL a couple; a second call repeats the bits."""
-    c, h, t = _cpl_case(name, gpu)
-    r = _cpl_run(name, gpu)
-    R = cpr.couple_scores_ref(_cpl_draws(name, gpu), c["targets"], c["pred"], c["members"], c["K"], c["B"], c["reach"])
-    _check_against(r, R, f"coupled, case {name}")
-    assert CPL_TOL <= 1e-4
-    again = _cpl_run(name, gpu)
-    assert torch.equal(again.per_couple, r.per_couple) and _same(again.per_frame_f, r.per_frame_f)
-    assert _same(again.sums, r.sums) and torch.equal(again.hist, r.hist) and torch.equal(again.tot, r.tot)
-    no = _cpl_run(name, gpu, want_per_couple=False, want_per_frame=False)
-    assert no.per_couple is None and _same(no.sums, r.sums) and torch.equal(no.hist, r.hist)
+    _cpl_parity(gpu, name)
+
+
+@pytest.mark.parametrize("at", BOUNDARY_SEEDS)
+def test_couple_scores_at_a_seed_whose_low_word_carries(gpu, at):
+    """Case k2 with the same assertions at the seeds where draw 1's seed carries
+    out of the low word (A = 2^32 - 1) and wraps to 0 (W = 2^64 - 1): the salt is
+    XORed into the halves after the carry (csrc/g2k_couples.hip,
+    CoupledHead::draw).  tests/test_coupled_head.py: the checker's integer
+    outputs change when the carry is dropped."""
+    _cpl_parity(gpu, "k2", BOUNDARY_SEEDS[at], f" seed {at}")
 
 
 @pytest.mark.parametrize("name", CPL)

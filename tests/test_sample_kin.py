@@ -18,6 +18,7 @@ from multimodaltraj_2_amd import _lib, kin, mixture, modes, ranks, scores
 from multimodaltraj_2_amd import build as g2k_build
 from tests import kin_cases as kc
 from tests import kin_ref as kr
+from tests.bestk_ref import SEED_A
 from tests import ranks_cases as rc
 from tests import ranks_ref as rr
 
@@ -281,6 +282,25 @@ def test_checker_against_plain_loops():
             assert np.all(m >= 0) and np.all(p >= 0) and np.all(p <= 2 * m + 1e-12)
             np.testing.assert_allclose(R["sums"], per[..., 32:].sum(axis=(1, 2)), rtol=0, atol=0)
     assert checked >= 30
+
+
+@pytest.mark.parametrize("which", kc.HEADS)
+def test_boundary_seed_ties_and_the_carry(which):
+    """Case k2 at seed A, whose low word carries at draw 1
+    (tests/test_sample_kin_gpu.py runs the kernel there): no fp32 tie between a
+    draw's feature and the target's on the restated draws, and the checker's
+    ranks and hist change when the draws are made with the carry dropped."""
+    i = kc.IDS.index("k2")
+    c = kc.inputs(i)
+    R, D = (kr.sample_kin_ref(kc.oracle_draws(i, which, SEED_A, carry), c["targets"], c["pairs"])
+            for carry in (True, False))
+    for v in (R, D):
+        assert int((v["fx"] == v["fy"][None]).sum()) == 0 and np.isfinite(v["per"]).all()
+    changed = int((R["per"][..., :32] != D["per"][..., :32]).sum())
+    hr, hd = (kr.hist_tot(v["per"], c["pairs"], c["K"], c["B"])[0] for v in (R, D))
+    moved = np.abs(R["sums"] - D["sums"]).max()
+    print(f"k2 seed A {which}: carry dropped, {changed} ranks change, sums move by {moved:.3g}")
+    assert changed > 0 and not np.array_equal(hr, hd) and moved > 1e-2
 
 
 def _band(xy):

@@ -18,7 +18,7 @@ import torch
 from tests import kin_cases as kc
 from tests import kin_ref as kr
 from tests.abi_arena import Arena, all_written
-from tests.bestk_ref import MASK64
+from tests.bestk_ref import MASK64, SEED_A
 from tests.scores_ref import TOL
 from tests.test_sample_kin import PROP, property_check
 
@@ -64,12 +64,17 @@ def _device_inputs(i, which, dev):
     return _DEV[(i, which)]
 
 
-def _run(i, which, dev, want_per_ped=True):
+def _key(i, which, seed):
+    """The caches' key: the case's own seed (None), or another."""
+    return (i, which) if seed is None else (i, which, seed)
+
+
+def _run(i, which, dev, want_per_ped=True, seed=None):
     c = kc.inputs(i)
     h, t = _device_inputs(i, which, dev)
-    r = h.sample_kin(t["pred"], t["targets"], t["n_active"], c["K"], c["B"], seed=c["seed"],
-                     n_frames=t["n_frames"], ped_mask=t["ped_mask"], want_per_ped=want_per_ped,
-                     targets_shared=c["shared"])
+    r = h.sample_kin(t["pred"], t["targets"], t["n_active"], c["K"], c["B"],
+                     seed=c["seed"] if seed is None else seed, n_frames=t["n_frames"], ped_mask=t["ped_mask"],
+                     want_per_ped=want_per_ped, targets_shared=c["shared"])
     torch.cuda.synchronize()
     return r
 
@@ -77,21 +82,24 @@ def _run(i, which, dev, want_per_ped=True):
 _RES, _REF = {}, {}
 
 
-def _result(i, which, dev):
-    if (i, which) not in _RES:
-        _RES[(i, which)] = _run(i, which, dev)
-    return _RES[(i, which)]
+def _result(i, which, dev, seed=None):
+    key = _key(i, which, seed)
+    if key not in _RES:
+        _RES[key] = _run(i, which, dev, seed=seed)
+    return _RES[key]
 
 
-def _recount(i, which, dev):
+def _recount(i, which, dev, seed=None):
     """The checker over the device's own K draws (computed once)."""
-    if (i, which) not in _REF:
+    key = _key(i, which, seed)
+    if key not in _REF:
         c = kc.inputs(i)
         h, t = _device_inputs(i, which, dev)
-        draws = np.stack([h.sample(t["pred"], seed=(c["seed"] + k) & MASK64).cpu().numpy()
+        s0 = c["seed"] if seed is None else seed
+        draws = np.stack([h.sample(t["pred"], seed=(s0 + k) & MASK64).cpu().numpy()
                           for k in range(c["K"])])
-        _REF[(i, which)] = kr.sample_kin_ref(draws.astype(np.float32), c["targets"], c["pairs"])
-    return _REF[(i, which)]
+        _REF[key] = kr.sample_kin_ref(draws.astype(np.float32), c["targets"], c["pairs"])
+    return _REF[key]
 
 
 def _check_against(per, sums, hist, tot, R, K, B, label):
@@ -116,14 +124,13 @@ def _check_against(per, sums, hist, tot, R, K, B, label):
     assert np.all(np.abs(sums - R["sums"]) <= TOL * n * np.maximum(1.0, np.abs(R["sums"])))
 
 
-@pytest.mark.parametrize("i,which", ALL, ids=ALL_IDS)
-def test_ranks_equal_and_sums_within_tolerance(gpu, i, which):
+def _parity(dev, i, which, seed=None, label=""):
     c = kc.inputs(i)
-    r, R = _result(i, which, gpu), _recount(i, which, gpu)
+    r, R = _result(i, which, dev, seed), _recount(i, which, dev, seed)
     per = r.per_ped.cpu().numpy().astype(np.float64)
     sums = r.sums.cpu().numpy().astype(np.float64)
     hist, tot = r.hist.cpu().numpy().astype(np.int64), r.tot.cpu().numpy()
-    _check_against(per, sums, hist, tot, R, c["K"], c["B"], f"case {kc.IDS[i]} {which}")
+    _check_against(per, sums, hist, tot, R, c["K"], c["B"], f"case {kc.IDS[i]} {which}{label}")
     # the result class's figures are the counts'
     assert r.k == c["K"] and r.bins == c["B"] and r.pairs == int(c["pairs"].sum())
     want = kr.figures(sums, hist, tot, c["K"])
@@ -132,6 +139,21 @@ def test_ranks_equal_and_sums_within_tolerance(gpu, i, which):
                          ("target_mean", r.target_mean)):
             assert fn(g) == pytest.approx(want[g][name], rel=1e-12, abs=1e-12), (g, name)
         assert 0.0 <= r.dev(g) <= 1.0 and 0.0 <= r.pit_mean(g) <= 1.0
+
+
+@pytest.mark.parametrize("i,which", ALL, ids=ALL_IDS)
+def test_ranks_equal_and_sums_within_tolerance(gpu, i, which):
+    _parity(gpu, i, which)
+
+
+@pytest.mark.parametrize("which", kc.HEADS)
+def test_seed_whose_low_word_carries(gpu, which):
+    """Case k2 with the same assertions at seed A = 2^32 - 1, where draw 1's
+    seed carries out of the low word: the launcher's split of the seed and
+    drawn_lane's lo / hi arithmetic (csrc/g2k_drawn.h) against the samplers' at
+    (seed + k) mod 2^64.  tests/test_sample_kin.py: the checker's integer
+    outputs change when the carry is dropped."""
+    _parity(gpu, kc.IDS.index("k2"), which, SEED_A, " seed A")
 
 
 def _raw_call(i, which, dev, per_ped, sums, hist, tot, t=None, ws=None):

@@ -19,7 +19,7 @@ from tests import bestk_ref
 from tests import fullcov_ref
 from tests import modes_cases as mc
 from tests import modes_ref as mo
-from tests.bestk_ref import MASK64
+from tests.bestk_ref import MASK64, SEED_A
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "g2k_modes.h")
@@ -406,6 +406,25 @@ def test_fragile_share_is_within_the_cap():
         assert frag <= mo.FRAGILE_SHARE * n, (mc.IDS[i], which, frag, n)
         assert np.isfinite(R["per_ped"]).all() and np.isfinite(R["out"]).all()
         assert np.isfinite(R["centres"]).all()
+
+
+def test_boundary_seed_margins_and_the_carry():
+    """Case mk (tests/modes_cases.BOUNDARY_ROW says why not m1) at seed A, whose
+    low word carries at draw 1 (tests/test_sample_modes_gpu.py runs the kernel
+    there): no fragile pair on the restated draws, and the checker's integer
+    outputs (mA, mF) change when the draws are made with the carry dropped."""
+    for which in mc.HEADS:
+        i = mc.IDS.index(mc.BOUNDARY_ROW)
+        c = mc.inputs(i)
+        m = c["pairs"]
+        R, D = (mo.sample_modes_ref(mc.oracle_draws(i, which, SEED_A, carry), c["targets"], m, c["M"], c["iters"],
+                                    mc.MISS_RADIUS) for carry in (True, False))
+        for v in (R, D):
+            assert int((v["margin"][m] < mo.FRAGILE).sum()) == 0 and np.isfinite(v["per_ped"]).all()
+        changed = int((R["per_ped"][m][:, [2, 3, 7]] != D["per_ped"][m][:, [2, 3, 7]]).sum())
+        moved = np.abs(R["out"][:, :7] - D["out"][:, :7]).max()
+        print(f"mk seed A {which}: carry dropped, {changed} of mA, mF, live change, the scene sums move by {moved:.3g}")
+        assert changed > 0 and moved > 1e-2
 
 
 def test_figures():

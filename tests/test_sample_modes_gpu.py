@@ -28,7 +28,7 @@ from tests import bestk_ref
 from tests import modes_cases as mc
 from tests import modes_ref as mo
 from tests.abi_arena import Arena, all_written
-from tests.bestk_ref import MASK64
+from tests.bestk_ref import MASK64, SEED_A
 
 pytestmark = pytest.mark.gpu
 STEMS = {"per_step": "g2k_sample_modes", "fullcov": "g2k_fullcov_sample_modes",
@@ -66,12 +66,17 @@ def _device_inputs(i, which, dev):
     return _DEV[(i, which)]
 
 
-def _run(i, which, dev, want_per_ped=True, want_centres=True, head=None):
+def _key(i, which, seed):
+    """The caches' key: the case's own seed (None), or another."""
+    return (i, which) if seed is None else (i, which, seed)
+
+
+def _run(i, which, dev, want_per_ped=True, want_centres=True, head=None, seed=None):
     c = mc.inputs(i)
     h, t = _device_inputs(i, which, dev)
     r = (head or h).sample_modes(t["pred"], t["targets"], t["n_active"], c["K"], c["M"], c["iters"],
-                                 seed=c["seed"], miss_radius=mc.MISS_RADIUS, n_frames=t["n_frames"],
-                                 ped_mask=t["ped_mask"], want_per_ped=want_per_ped,
+                                 seed=c["seed"] if seed is None else seed, miss_radius=mc.MISS_RADIUS,
+                                 n_frames=t["n_frames"], ped_mask=t["ped_mask"], want_per_ped=want_per_ped,
                                  want_centres=want_centres, targets_shared=c["shared"])
     torch.cuda.synchronize()
     return r
@@ -80,32 +85,33 @@ def _run(i, which, dev, want_per_ped=True, want_centres=True, head=None):
 _RES, _REF = {}, {}
 
 
-def _result(i, which, dev):
-    if (i, which) not in _RES:
-        _RES[(i, which)] = _run(i, which, dev)
-    return _RES[(i, which)]
+def _result(i, which, dev, seed=None):
+    key = _key(i, which, seed)
+    if key not in _RES:
+        _RES[key] = _run(i, which, dev, seed=seed)
+    return _RES[key]
 
 
-def _recount(i, which, dev):
+def _recount(i, which, dev, seed=None):
     """The float64 checker over the device's own K draws (computed once)."""
-    if (i, which) not in _REF:
+    key = _key(i, which, seed)
+    if key not in _REF:
         c = mc.inputs(i)
         h, t = _device_inputs(i, which, dev)
-        draws = np.stack([h.sample(t["pred"], seed=(c["seed"] + k) & MASK64).cpu().numpy()
+        s0 = c["seed"] if seed is None else seed
+        draws = np.stack([h.sample(t["pred"], seed=(s0 + k) & MASK64).cpu().numpy()
                           for k in range(c["K"])])
-        _REF[(i, which)] = mo.sample_modes_ref(draws, c["targets"], c["pairs"], c["M"], c["iters"],
-                                               mc.MISS_RADIUS)
-    return _REF[(i, which)]
+        _REF[key] = mo.sample_modes_ref(draws, c["targets"], c["pairs"], c["M"], c["iters"], mc.MISS_RADIUS)
+    return _REF[key]
 
 
 def _gate(ref, tol=mo.TOL):
     return tol * np.maximum(1.0, np.abs(ref))
 
 
-@pytest.mark.parametrize("i,which", mc.ALL, ids=mc.ALL_IDS)
-def test_recount_from_the_devices_own_draws(gpu, i, which):
+def _parity(dev, i, which, seed=None, label=""):
     c = mc.inputs(i)
-    r, R = _result(i, which, gpu), _recount(i, which, gpu)
+    r, R = _result(i, which, dev, seed), _recount(i, which, dev, seed)
     m = c["pairs"]
     n = int(m.sum())
     # the cap on fragile pairs: a condition on the inputs, on the device's draws
@@ -124,7 +130,7 @@ def test_recount_from_the_devices_own_draws(gpu, i, which):
     e_w = np.abs(P[:, 4:6] - Rp[:, 4:6]).max(initial=0.0)
     cg, cr = np.moveaxis(cen, 4, 2)[ok], np.moveaxis(R["centres"], 4, 2)[ok]     # [P, M, 24]
     e_cen = (np.abs(cg - cr) / _gate(cr, 1e-5)).max(initial=0.0)
-    print(f"case {mc.IDS[i]} {which}: {n} pairs, {int(frag.sum())} fragile (smallest margin "
+    print(f"case {mc.IDS[i]} {which}{label}: {n} pairs, {int(frag.sum())} fragile (smallest margin "
           f"{R['margin'][m].min() if n else float('inf'):.3g}); worst |kernel - float64| / gate: cA, cF, "
           f"inertia {e_val:.3g}, centres {e_cen:.3g}; weights of the best centres off by {e_w:.3g}")
     assert e_val <= 1.0
@@ -167,6 +173,22 @@ def test_recount_from_the_devices_own_draws(gpu, i, which):
         assert r.miss_radius == mc.MISS_RADIUS
     else:
         assert np.isnan(r.min_ade) and np.isnan(r.miss_rate) and r.pairs == 0
+
+
+@pytest.mark.parametrize("i,which", mc.ALL, ids=mc.ALL_IDS)
+def test_recount_from_the_devices_own_draws(gpu, i, which):
+    _parity(gpu, i, which)
+
+
+@pytest.mark.parametrize("which", mc.HEADS)
+def test_seed_whose_low_word_carries(gpu, which):
+    """Case mk (tests/modes_cases.BOUNDARY_ROW) with the same assertions at seed
+    A = 2^32 - 1, where draw 1's seed carries out of the low word: the
+    launcher's split of the seed and drawn_lane's lo / hi arithmetic
+    (csrc/g2k_drawn.h) against the samplers' at (seed + k) mod 2^64.
+    tests/test_sample_modes.py: the checker's integer outputs change when the
+    carry is dropped."""
+    _parity(gpu, mc.IDS.index(mc.BOUNDARY_ROW), which, SEED_A, " seed A")
 
 
 @pytest.mark.parametrize("which", mc.HEADS)

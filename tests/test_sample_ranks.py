@@ -20,6 +20,7 @@ from multimodaltraj_2_amd import build as g2k_build
 from oracle import g2k_ref as ref
 from tests import ranks_cases as rc
 from tests import ranks_ref as rr
+from tests.bestk_ref import SEED_A
 from tests.bestk_ref import MASK64
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -299,6 +300,28 @@ def test_margins_and_wide_interval_cap_on_the_oracles_draws():
             worst = max(worst, dv)
     print(f"worst deviation {worst:.3g} (recorded {rr.MEASURED}), M = {rr.M}")
     assert worst <= rr.MEASURED
+
+
+@pytest.mark.parametrize("which", rc.HEADS)
+def test_boundary_seed_intervals_and_the_carry(which):
+    """Case k4 at seed A, whose low word carries at draw 1
+    (tests/test_sample_ranks_gpu.py runs the kernel there): the wide-interval
+    cap and no degenerate step on the restated draws, and the checker's ranks
+    change when the draws are made with the carry dropped."""
+    i = rc.IDS.index("k4")
+    c = rc.inputs(i)
+    R, D = (rr.sample_ranks_ref(rc.oracle_draws(i, which, SEED_A, carry), c["targets"], c["pairs"])
+            for carry in (True, False))
+    for v in (R, D):
+        assert float((v["r_hi"] > v["r_lo"])[c["pairs"]].mean()) <= rr.WIDE_CAP
+        assert not v["deg"].any() and not v["deg_open"][c["pairs"]].any()
+    dv = rr.deviation(rc.oracle_draws(i, which, SEED_A), c["targets"], c["pairs"], c["pred"], which == "mix")
+    assert dv <= rr.MEASURED
+    # the ranks change by more than any interval's width allows: outside the right draws' intervals
+    out = c["pairs"][..., None] & ((D["r"] < R["r_lo"]) | (D["r"] > R["r_hi"]))
+    print(f"k4 seed A {which}: carry dropped, {int((D['r'] != R['r']).sum())} ranks change, {int(out.sum())} "
+          f"leave their interval")
+    assert out.sum() > 0
 
 
 # ---------------------------------------------------------------------------

@@ -19,7 +19,7 @@ import torch
 from tests import ranks_cases as rc
 from tests import ranks_ref as rr
 from tests.abi_arena import Arena, all_written
-from tests.bestk_ref import MASK64
+from tests.bestk_ref import MASK64, SEED_A
 
 pytestmark = pytest.mark.gpu
 ALL = [(i, w) for i in range(len(rc.CASES)) for w in rc.HEADS]
@@ -63,12 +63,17 @@ def _device_inputs(i, which, dev):
     return _DEV[(i, which)]
 
 
-def _run(i, which, dev, want_per_ped=True):
+def _key(i, which, seed):
+    """The caches' key: the case's own seed (None), or another."""
+    return (i, which) if seed is None else (i, which, seed)
+
+
+def _run(i, which, dev, want_per_ped=True, seed=None):
     c = rc.inputs(i)
     h, t = _device_inputs(i, which, dev)
-    r = h.sample_ranks(t["pred"], t["targets"], t["n_active"], c["K"], c["B"], seed=c["seed"],
-                       n_frames=t["n_frames"], ped_mask=t["ped_mask"], want_per_ped=want_per_ped,
-                       targets_shared=c["shared"])
+    r = h.sample_ranks(t["pred"], t["targets"], t["n_active"], c["K"], c["B"],
+                       seed=c["seed"] if seed is None else seed, n_frames=t["n_frames"], ped_mask=t["ped_mask"],
+                       want_per_ped=want_per_ped, targets_shared=c["shared"])
     torch.cuda.synchronize()
     return r
 
@@ -76,21 +81,24 @@ def _run(i, which, dev, want_per_ped=True):
 _RES, _REF = {}, {}
 
 
-def _result(i, which, dev):
-    if (i, which) not in _RES:
-        _RES[(i, which)] = _run(i, which, dev)
-    return _RES[(i, which)]
+def _result(i, which, dev, seed=None):
+    key = _key(i, which, seed)
+    if key not in _RES:
+        _RES[key] = _run(i, which, dev, seed=seed)
+    return _RES[key]
 
 
-def _recount(i, which, dev):
+def _recount(i, which, dev, seed=None):
     """The float64 checker over the device's own K draws (computed once)."""
-    if (i, which) not in _REF:
+    key = _key(i, which, seed)
+    if key not in _REF:
         c = rc.inputs(i)
         h, t = _device_inputs(i, which, dev)
-        draws = np.stack([h.sample(t["pred"], seed=(c["seed"] + k) & MASK64).cpu().numpy()
+        s0 = c["seed"] if seed is None else seed
+        draws = np.stack([h.sample(t["pred"], seed=(s0 + k) & MASK64).cpu().numpy()
                           for k in range(c["K"])])
-        _REF[(i, which)] = rr.sample_ranks_ref(draws, c["targets"], c["pairs"])
-    return _REF[(i, which)]
+        _REF[key] = rr.sample_ranks_ref(draws, c["targets"], c["pairs"])
+    return _REF[key]
 
 
 def _check_against(per, hist, tot, R, K, B, label):
@@ -132,13 +140,12 @@ def _check_against(per, hist, tot, R, K, B, label):
             assert int((hi[..., i][both[..., i]] < b * w).sum()) <= got <= int((lo[..., i][both[..., i]] < b * w).sum())
 
 
-@pytest.mark.parametrize("i,which", ALL, ids=ALL_IDS)
-def test_ranks_inside_the_checkers_intervals(gpu, i, which):
+def _parity(dev, i, which, seed=None, label=""):
     c = rc.inputs(i)
-    r, R = _result(i, which, gpu), _recount(i, which, gpu)
+    r, R = _result(i, which, dev, seed), _recount(i, which, dev, seed)
     per = r.per_ped.cpu().numpy().astype(np.float64)
     hist, tot = r.hist.cpu().numpy().astype(np.int64), r.tot.cpu().numpy()
-    _check_against(per, hist, tot, R, c["K"], c["B"], f"case {rc.IDS[i]} {which}")
+    _check_against(per, hist, tot, R, c["K"], c["B"], f"case {rc.IDS[i]} {which}{label}")
     # the result class's figures are the counts'
     assert r.k == c["K"] and r.bins == c["B"] and r.pairs == int(c["pairs"].sum())
     if c["pairs"].any():
@@ -149,6 +156,21 @@ def test_ranks_inside_the_checkers_intervals(gpu, i, which):
         assert r.degenerate_share == 0.0 and 0.0 <= r.dev <= 1.0 and 0.0 <= r.dev_traj <= 1.0
     else:
         assert np.isnan(r.dev)
+
+
+@pytest.mark.parametrize("i,which", ALL, ids=ALL_IDS)
+def test_ranks_inside_the_checkers_intervals(gpu, i, which):
+    _parity(gpu, i, which)
+
+
+@pytest.mark.parametrize("which", rc.HEADS)
+def test_seed_whose_low_word_carries(gpu, which):
+    """Case k4 with the same assertions at seed A = 2^32 - 1, where draw 1's
+    seed carries out of the low word: the launcher's split of the seed and
+    drawn_lane's lo / hi arithmetic (csrc/g2k_drawn.h) against the samplers' at
+    (seed + k) mod 2^64.  tests/test_sample_ranks.py: the checker's ranks
+    change when the carry is dropped."""
+    _parity(gpu, rc.IDS.index("k4"), which, SEED_A, " seed A")
 
 
 def _raw_call(i, which, dev, per_ped, hist, tot, t=None, ws=None):

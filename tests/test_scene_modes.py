@@ -25,6 +25,7 @@ from tests import couples_cases as cc
 from tests import fullcov_ref as fr
 from tests import scene_modes_cases as mc
 from tests import scene_modes_ref as mr
+from tests.bestk_ref import BOUNDARY_SEEDS
 from tests import scene_ranks_cases as sc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -382,6 +383,31 @@ def test_the_cases_meet_their_two_conditions():
             if name in ("n256", "k32", "k2"):
                 assert np.all(R["counts"][scored] == 1)
     assert frames == 4 * (5 + 5 + 6 + 2 + 1 + 6 + 1 + 2 + 6 + 6) and 0 < missed < frames
+
+
+@pytest.mark.parametrize("which", mc.HEADS)
+@pytest.mark.parametrize("at", BOUNDARY_SEEDS)
+def test_boundary_seeds_meet_the_conditions_and_see_the_carry(at, which):
+    """Case k2 at the seeds whose low word carries at draw 1 (tests/bestk_ref.py;
+    tests/test_scene_modes_gpu.py runs the kernel there): no ambiguous argmin or
+    argmax, the poison never read, k2's own claims (the exact tie takes draw 0;
+    M = K: every draw a medoid), and the checker's integer outputs change when
+    draw 1 is made with the carry dropped."""
+    i, seed = mc.IDS.index("k2"), BOUNDARY_SEEDS[at]
+    c = mc.inputs(i)
+    R, D = (mr.scene_modes_ref(mc.oracle_draws(i, which, seed, carry), c["targets"], c["members"], c["K"], c["M"],
+                               c["iters"], c["radius"]) for carry in (True, False))
+    for v in (R, D):
+        assert not v["ambiguous"].any()
+        assert v["frames"] == int((c["members"].sum(axis=2) >= 1).sum())
+        assert np.isfinite(v["per_frame_d"]).all() and np.isfinite(v["sums"]).all()
+        scored = v["per_frame_i"][..., 0] > 0
+        assert np.all(v["medoids"][scored][:, 0] == 0) and np.all(v["medoids"][scored][:, 1] == 1)
+        assert np.all(v["counts"][scored] == 1)
+    changed = {k: int((R[k] != D[k]).sum()) for k in ("per_frame_i", "medoids", "counts", "tot")}
+    moved = np.abs(R["sums"] - D["sums"]).max()
+    print(f"k2 seed {at} {which}: carry dropped, integers changed {changed}, sums move by {moved:.3g}")
+    assert changed["per_frame_i"] + changed["tot"] > 0 and moved > 1e-2
 
 
 def test_the_result_class():

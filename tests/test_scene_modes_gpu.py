@@ -24,7 +24,7 @@ from tests import scene_modes_cases as mc
 from tests import scene_modes_ref as mr
 from tests import scene_ranks_cases as sc
 from tests.abi_arena import Arena, all_written
-from tests.bestk_ref import MASK64
+from tests.bestk_ref import BOUNDARY_SEEDS, MASK64
 
 pytestmark = pytest.mark.gpu
 ALL = [(i, w) for i in range(len(mc.CASES)) for w in mc.HEADS]
@@ -77,44 +77,52 @@ def _device_inputs(i, which, dev):
     return _DEV[(b, which)]
 
 
-def _run(i, which, dev, want_per_frame=True, want_modes=True, stream=None):
+def _key(i, which, seed):
+    """The caches' key: the case's own seed (None), or another."""
+    return (i, which) if seed is None else (i, which, seed)
+
+
+def _run(i, which, dev, want_per_frame=True, want_modes=True, stream=None, seed=None):
     c = mc.inputs(i)
     h, t = _device_inputs(i, which, dev)
     r = h.scene_modes(t["pred"], t["targets"], t["n_active"], c["K"], c["M"], c["iters"], c["radius"],
-                      seed=c["seed"], n_frames=t["n_frames"], ped_mask=t["ped_mask"],
+                      seed=c["seed"] if seed is None else seed, n_frames=t["n_frames"], ped_mask=t["ped_mask"],
                       want_per_frame=want_per_frame, want_modes=want_modes, targets_shared=c["shared"],
                       stream=stream)
     torch.cuda.synchronize()
     return r
 
 
-def _result(i, which, dev):
-    if (i, which) not in _RES:
-        _RES[(i, which)] = _run(i, which, dev)
-    return _RES[(i, which)]
+def _result(i, which, dev, seed=None):
+    key = _key(i, which, seed)
+    if key not in _RES:
+        _RES[key] = _run(i, which, dev, seed=seed)
+    return _RES[key]
 
 
-def _draws(i, which, dev):
+def _draws(i, which, dev, seed=None):
     """The device's own K joint draws [K, S, F, 24, N] float32 (made once per shape)."""
-    b = mc.base(i)
-    if (b, which) not in _DRAWS:
+    key = _key(mc.base(i), which, seed)
+    if key not in _DRAWS:
         c = mc.inputs(i)
         h, t = _device_inputs(i, which, dev)
-        _DRAWS[(b, which)] = np.stack([h.sample(t["pred"], seed=(c["seed"] + k) & MASK64).cpu().numpy()
-                                       for k in range(c["K"])]).astype(np.float32)
-    return _DRAWS[(b, which)]
+        s0 = c["seed"] if seed is None else seed
+        _DRAWS[key] = np.stack([h.sample(t["pred"], seed=(s0 + k) & MASK64).cpu().numpy()
+                                for k in range(c["K"])]).astype(np.float32)
+    return _DRAWS[key]
 
 
-def _recount(i, which, dev):
+def _recount(i, which, dev, seed=None):
     """The checker over the device's own K draws (computed once)."""
-    if (i, which) not in _REF:
+    key = _key(i, which, seed)
+    if key not in _REF:
         c = mc.inputs(i)
-        _REF[(i, which)] = mr.scene_modes_ref(_draws(i, which, dev), c["targets"], c["members"], c["K"], c["M"],
-                                              c["iters"], c["radius"])
-    return _REF[(i, which)]
+        _REF[key] = mr.scene_modes_ref(_draws(i, which, dev, seed), c["targets"], c["members"], c["K"], c["M"],
+                                       c["iters"], c["radius"])
+    return _REF[key]
 
 
-def _check_against(r, R, label):
+def _check_against(r, R, label, worst=_WORST):
     """The doubles within TOL of the checker's, the integers equal to it,
     outside the scene-frames the checker marks ambiguous; tot the rows' own
     recount."""
@@ -127,11 +135,11 @@ def _check_against(r, R, label):
     serr = np.abs(sums - R["sums"]) / np.maximum(1.0, np.abs(R["sums"]))
     off = int((pi[keep] != R["per_frame_i"][keep]).sum() + (med[keep] != R["medoids"][keep]).sum()
               + (cnt[keep] != R["counts"][keep]).sum())
-    worst = float(err[keep].max()) if err[keep].size else 0.0
+    worst_d = float(err[keep].max()) if err[keep].size else 0.0
     print(f"{label}: {R['frames']} scene-frames scored, {int(R['ambiguous'].sum())} left out as ambiguous; worst "
-          f"error of per_frame_d {worst:.3g}, of sums {serr.max() if serr.size else 0.0:.3g} (tolerance {TOL:g}); "
+          f"error of per_frame_d {worst_d:.3g}, of sums {serr.max() if serr.size else 0.0:.3g} (tolerance {TOL:g}); "
           f"{off} integers off the checker's own")
-    _WORST[label] = (worst, float(serr.max()) if serr.size else 0.0, R["frames"], int(R["ambiguous"].sum()))
+    worst[label] = (worst_d, float(serr.max()) if serr.size else 0.0, R["frames"], int(R["ambiguous"].sum()))
     assert pd.dtype == np.float64 and np.isfinite(pd).all() and np.isfinite(sums).all()
     assert np.all(err[keep] <= TOL)
     np.testing.assert_array_equal(pi[keep], R["per_frame_i"][keep])
@@ -148,11 +156,10 @@ def _check_against(r, R, label):
         assert np.all(serr <= TOL)
 
 
-@pytest.mark.parametrize("i,which", ALL, ids=ALL_IDS)
-def test_doubles_within_tolerance_and_integers_equal(gpu, i, which):
+def _parity(dev, i, which, seed=None, label="", worst=_WORST):
     c = mc.inputs(i)
-    r, R = _result(i, which, gpu), _recount(i, which, gpu)
-    _check_against(r, R, f"case {mc.IDS[i]} {which}")
+    r, R = _result(i, which, dev, seed), _recount(i, which, dev, seed)
+    _check_against(r, R, f"case {mc.IDS[i]} {which}{label}", worst)
     assert (r.k, r.modes, r.iters) == (c["K"], c["M"], c["iters"])
     assert r.frames == int((c["members"].sum(axis=2) >= 1).sum())
     # the result class's figures are the sums'
@@ -162,6 +169,24 @@ def test_doubles_within_tolerance_and_integers_equal(gpu, i, which):
     assert r.all_jade <= r.jade and r.all_jade <= r.raw_jade and 0.0 <= r.miss_rate <= 1.0
     if c["M"] == c["K"]:
         assert r.jade == r.all_jade and r.cost == 0.0
+
+
+@pytest.mark.parametrize("i,which", ALL, ids=ALL_IDS)
+def test_doubles_within_tolerance_and_integers_equal(gpu, i, which):
+    _parity(gpu, i, which)
+
+
+@pytest.mark.parametrize("which", mc.HEADS)
+@pytest.mark.parametrize("at", BOUNDARY_SEEDS)
+def test_seed_whose_low_word_carries(gpu, at, which):
+    """Case k2 with the same assertions at the seeds where draw 1's seed carries
+    out of the low word (A = 2^32 - 1) and wraps to 0 (W = 2^64 - 1): the kernel's
+    own lo / hi arithmetic (csrc/g2k_scene_modes.hip) against the samplers' at
+    (seed + k) mod 2^64; for the coupled head the salt is XORed in after the
+    carry.  tests/test_scene_modes.py: the restated draws leave no scene-frame
+    ambiguous there, and the checker's integer outputs change when the carry
+    is dropped."""
+    _parity(gpu, mc.IDS.index("k2"), which, BOUNDARY_SEEDS[at], f" seed {at}", worst={})
 
 
 def test_scene_frames_left_out_as_ambiguous(gpu):

@@ -22,6 +22,7 @@ from tests import couples_cases as cc
 from tests import fullcov_ref as fr
 from tests import scene_ranks_cases as sc
 from tests import scene_ranks_ref as sr
+from tests.bestk_ref import BOUNDARY_SEEDS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "g2k_scene_ranks.h")
@@ -366,6 +367,29 @@ def test_the_checker_alone_meets_the_interval_condition():
             assert np.isfinite(R["per_frame_d"]).all()                  # the poison was never read
             n += R["ranks"]
     assert n == 4 * 3 * 21
+
+
+@pytest.mark.parametrize("at,which,row", sc.BOUNDARY, ids=sc.BOUNDARY_IDS)
+def test_boundary_seeds_meet_the_interval_condition_and_see_the_carry(at, which, row):
+    """Case k2 (k20 where tests/scene_ranks_cases.py says why) at the seeds whose
+    low word carries at draw 1 (tests/bestk_ref.py; tests/test_scene_ranks_gpu.py
+    runs the kernel there): the interval condition as above, and the checker's
+    integer outputs change when draw 1 is made with the carry dropped — the GPU
+    test would see a kernel that dropped it."""
+    i, seed = sc.IDS.index(row), BOUNDARY_SEEDS[at]
+    c = sc.inputs(i)
+    R = sr.scene_ranks_ref(sc.oracle_draws(i, which, seed), c["targets"], c["pred"], c["members"], c["K"], c["B"])
+    assert R["wide"] == 0 and R["ties"] == 0 and R["ranks"] == 3 * int((c["members"].sum(axis=2) >= 2).sum())
+    assert np.isfinite(R["per_frame_d"]).all()
+    D = sr.scene_ranks_ref(sc.oracle_draws(i, which, seed, carry=False), c["targets"], c["pred"], c["members"],
+                           c["K"], c["B"])
+    assert D["wide"] == 0 and D["ties"] == 0
+    moved = np.abs(D["sums"] - R["sums"]).max()
+    print(f"seed {at} {which}: carry dropped, sums move by {moved:.3g}, "
+          f"{int((D['per_frame_i'] != R['per_frame_i']).sum())} ranks change")
+    assert not (np.array_equal(D["per_frame_i"], R["per_frame_i"]) and np.array_equal(D["hist"], R["hist"])
+                and np.array_equal(D["tot"], R["tot"]))
+    assert moved > 1e-2
 
 
 @pytest.mark.parametrize("K,B", [(20, 21), (20, 7), (64, 13), (2, 3), (3, 1)])

@@ -21,7 +21,7 @@ from tests import couples_cases as cc
 from tests import scene_ranks_cases as sc
 from tests import scene_ranks_ref as sr
 from tests.abi_arena import Arena, all_written
-from tests.bestk_ref import MASK64
+from tests.bestk_ref import BOUNDARY_SEEDS, MASK64
 
 pytestmark = pytest.mark.gpu
 ALL = [(i, w) for i in range(len(sc.CASES)) for w in sc.HEADS]
@@ -72,39 +72,49 @@ def _device_inputs(i, which, dev):
     return _DEV[(i, which)]
 
 
-def _run(i, which, dev, want_per_frame=True, k=None, bins=None, stream=None):
+def _key(i, which, seed):
+    """The caches' key: the case's own seed (None), or another."""
+    return (i, which) if seed is None else (i, which, seed)
+
+
+def _run(i, which, dev, want_per_frame=True, k=None, bins=None, stream=None, seed=None):
     c = sc.inputs(i)
     h, t = _device_inputs(i, which, dev)
-    r = h.scene_ranks(t["pred"], t["targets"], t["n_active"], k or c["K"], bins or c["B"], seed=c["seed"],
+    r = h.scene_ranks(t["pred"], t["targets"], t["n_active"], k or c["K"], bins or c["B"],
+                      seed=c["seed"] if seed is None else seed,
                       n_frames=t["n_frames"], ped_mask=t["ped_mask"], want_per_frame=want_per_frame,
                       targets_shared=c["shared"], stream=stream)
     torch.cuda.synchronize()
     return r
 
 
-def _result(i, which, dev):
-    if (i, which) not in _RES:
-        _RES[(i, which)] = _run(i, which, dev)
-    return _RES[(i, which)]
+def _result(i, which, dev, seed=None):
+    key = _key(i, which, seed)
+    if key not in _RES:
+        _RES[key] = _run(i, which, dev, seed=seed)
+    return _RES[key]
 
 
-def _draws(i, which, dev):
+def _draws(i, which, dev, seed=None):
     """The device's own K joint draws [K, S, F, 24, N] float32 (made once)."""
-    if (i, which) not in _DRAWS:
+    key = _key(i, which, seed)
+    if key not in _DRAWS:
         c = sc.inputs(i)
         h, t = _device_inputs(i, which, dev)
-        _DRAWS[(i, which)] = np.stack([h.sample(t["pred"], seed=(c["seed"] + k) & MASK64).cpu().numpy()
-                                       for k in range(c["K"])]).astype(np.float32)
-    return _DRAWS[(i, which)]
+        s0 = c["seed"] if seed is None else seed
+        _DRAWS[key] = np.stack([h.sample(t["pred"], seed=(s0 + k) & MASK64).cpu().numpy()
+                                for k in range(c["K"])]).astype(np.float32)
+    return _DRAWS[key]
 
 
-def _recount(i, which, dev):
+def _recount(i, which, dev, seed=None):
     """The checker over the device's own K draws (computed once)."""
-    if (i, which) not in _REF:
+    key = _key(i, which, seed)
+    if key not in _REF:
         c = sc.inputs(i)
-        _REF[(i, which)] = sr.scene_ranks_ref(_draws(i, which, dev), c["targets"], c["pred"], c["members"],
-                                              c["K"], c["B"])
-    return _REF[(i, which)]
+        _REF[key] = sr.scene_ranks_ref(_draws(i, which, dev, seed), c["targets"], c["pred"], c["members"],
+                                       c["K"], c["B"])
+    return _REF[key]
 
 
 def _check_against(r, R, K, B, label):
@@ -130,11 +140,10 @@ def _check_against(r, R, K, B, label):
     np.testing.assert_array_equal(tot, t2)
 
 
-@pytest.mark.parametrize("i,which", ALL, ids=ALL_IDS)
-def test_floats_within_tolerance_and_ranks_inside_their_intervals(gpu, i, which):
+def _parity(dev, i, which, seed=None, label=""):
     c = sc.inputs(i)
-    r, R = _result(i, which, gpu), _recount(i, which, gpu)
-    _check_against(r, R, c["K"], c["B"], f"case {sc.IDS[i]} {which}")
+    r, R = _result(i, which, dev, seed), _recount(i, which, dev, seed)
+    _check_against(r, R, c["K"], c["B"], f"case {sc.IDS[i]} {which}{label}")
     assert r.k == c["K"] and r.bins == c["B"] and r.frames == int((c["members"].sum(axis=2) >= 2).sum())
     # the result class's figures are the counts'
     want = sr.figures(r.sums.cpu().numpy(), r.hist.cpu().numpy(), r.tot.cpu().numpy(), c["K"])
@@ -147,13 +156,30 @@ def test_floats_within_tolerance_and_ranks_inside_their_intervals(gpu, i, which)
         assert r.target(g) == pytest.approx(want[g]["target"], rel=1e-12)
 
 
+@pytest.mark.parametrize("i,which", ALL, ids=ALL_IDS)
+def test_floats_within_tolerance_and_ranks_inside_their_intervals(gpu, i, which):
+    _parity(gpu, i, which)
+
+
+@pytest.mark.parametrize("at,which,row", sc.BOUNDARY, ids=sc.BOUNDARY_IDS)
+def test_seed_whose_low_word_carries(gpu, at, which, row):
+    """The same parity, same bounds, at the seeds where draw 1's seed carries
+    out of the low word (A = 2^32 - 1) and wraps to 0 (W = 2^64 - 1): the kernel's
+    own lo / hi arithmetic (csrc/g2k_scene_ranks.hip) against the samplers' at
+    (seed + k) mod 2^64; for the coupled head the salt is XORed in after the
+    carry.  tests/test_scene_ranks.py: the checker's outputs change when the
+    carry is dropped."""
+    _parity(gpu, sc.IDS.index(row), which, BOUNDARY_SEEDS[at], f" seed {at}")
+
+
 def test_ranks_with_an_interval_of_more_than_one_value(gpu):
     """Over every case and head (computed above, or here): the count DESIGN
     records; zero is expected."""
     for i, which in ALL:
         _recount(i, which, gpu)
-    ranks = sum(R["ranks"] for R in _REF.values())
-    wide = sum(R["wide"] for R in _REF.values())
+    own = [R for key, R in _REF.items() if len(key) == 2]             # the cases' own seeds
+    ranks = sum(R["ranks"] for R in own)
+    wide = sum(R["wide"] for R in own)
     print(f"{ranks} ranks on the device's draws, {wide} with an interval of more than one value")
     assert ranks == 252 and wide * 1000 <= ranks
 
